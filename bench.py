@@ -8,10 +8,14 @@ sk_i = LE(sha256(LE32_32(i))) mod r (reference state-transition/src/util/interop
 device-resident table.  Inputs are generated on the GPU before timing (signing kernels) and are resident
 in host pinned staging; one step = one blsgpu_verify call = H2D + full verification + per-job results.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1|C2|C3|C4|C5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C1|C2|C3|C4|C5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N      (one rank per GPU)
 
-Prints one JSON line (rank 0).  Multi-GPU: each rank verifies its own 16,384 sets (weak scaling, no
+Prints one JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline figures;
+--full adds everything else the benchmark measures or checks (per-stage roofline, isolated-call latency, the parity
+leg against the oracle, the CPU baselines).  --dump-outputs DIR writes the per-job results of the last timed step to
+DIR/job_results.npy, so two builds can be compared output for output (the inputs are the same from run to run).
+Multi-GPU: each rank verifies its own 16,384 sets (weak scaling, no
 collective on the data path; gloo is used only for the barrier and the max-over-ranks of the timing).
 """
 import argparse
@@ -614,6 +618,13 @@ def main():
                     help="diagnostics: every branch of a run on one stream (each kernel alone on the chip)")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="any other runtime option (blsgpu_set_option), e.g. --set coop_max=1024; repeatable")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: per-stage events and the roofline, the "
+                         "isolated-call latency, the parity leg and the CPU baselines (each can be switched off with "
+                         "its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the per-job results the last timed step returned to "
+                         "DIR/job_results.npy (float32; job_results_rankR.npy under a multi-process launcher)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
@@ -708,7 +719,7 @@ def main():
             raise SystemExit(f"verification mismatch on {len(bad)} jobs (first {bad[:8]}: got {res[bad[:8]]}, "
                              f"want {expected[bad[:8]]}); call {i}, variant {i % n_var}, run stats {fields}; "
                              f"re-verified: {len(bad2)} mismatches, same jobs {np.array_equal(bad, bad2)}")
-        return st, lat_ms
+        return st, lat_ms, res
 
     pool = ThreadPoolExecutor(max_workers=max(1, args.inflight, 4 * ctx.get_option("slots") + 4))
     for _ in range(args.warmup):
@@ -743,7 +754,8 @@ def main():
     except Exception:  # torch is plumbing only; every step is complete when its call returns
         sync = lambda: None
     # per-stage HIP events on each slot's stream, recorded by the runtime during the timed region (roofline)
-    if not args.no_profile:
+    profile = args.full and not args.no_profile
+    if profile:
         ctx.set_option("profile", 1)
     # ---- timed region: K steps, up to `inflight` of them on the GPU at once ----
     barrier()
@@ -769,7 +781,12 @@ def main():
     for tid, (nm, c1) in thr1.items():
         by_thread[nm] = by_thread.get(nm, 0.0) + c1 - thr0.get(tid, (nm, 0.0))[1]
     w1 = time.monotonic_ns()
-    ctx.set_option("profile", 0)
+    if profile:
+        ctx.set_option("profile", 0)
+    if args.dump_outputs:  # what the caller of the last timed step received: one result per job
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "job_results" if world == 1 else f"job_results_rank{rank}"
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), results[-1][2].astype(np.float32))
     stats = [r[0] for r in results]
     # re-checked jobs over the timed calls (a run's count is reported to each of its calls): 0 for an all-valid
     # workload unless a batch group's equation failed for valid sets
@@ -782,12 +799,6 @@ def main():
     total_sets = (desc["total_sets_per_step"] if strong else n_sets * world) * args.steps
     n_gpus = world * n_dev
     value = total_sets / dt
-    # ---- isolated batches (untimed): p50 latency of one call alone, and its per-stage kernel times ----
-    lat = []
-    for _ in range(3):
-        st_iso, l_ms = step()
-        lat.append(l_ms)
-    groups, n_msgs = st_iso.groups, st_iso.unique_messages  # one call alone: its own groups / distinct messages
     runs_timed = [st for st in stats if st.run_sets > 0]
     out = {
         "metric": "verified signature sets/sec (node)",
@@ -804,14 +815,12 @@ def main():
         "dtype": "u32/u64 (28-bit-limb Montgomery integer arithmetic)",
         "data": f"synthetic (interop keys, SHA-256 messages, signatures generated on the GPU before timing; "
                 f"{n_var} message variants, one per in-flight call, so merged runs share no signing root)",
-        "config": dict(desc, group_sets=args.group_sets, group_policy=args.group_policy,
-                       batch_groups_per_step=groups, inflight=args.inflight,
+        "config": dict(desc, group_sets=args.group_sets, group_policy=args.group_policy, inflight=args.inflight,
                        slots=ctx.get_option("slots"), hw_queues=ctx.get_option("hw_queues"),
                        merge_sets=args.merge_sets, pipeline_depth=ctx.get_option("pipeline_depth"),
                        merge_wait_us=ctx.get_option("merge_wait_us"), idle_wait_us=ctx.get_option("idle_wait_us"),
                        pipeline_runs_timed=len(runs_timed),
                        parallelism=f"shard-by-job x{n_gpus} ({'one process per GPU' if world > 1 else 'in-process devices'}), no collective"),
-        "p50_batch_latency_ms": round(float(np.median(lat)), 3),
         "fallback_jobs_timed": fallback_jobs_timed,
         "spurious_groups": ctx.get_option("spurious_groups"),
         # host cost of the timed region: CPU seconds of the whole process per million sets verified, and each run's
@@ -827,7 +836,16 @@ def main():
     }
     if urgent is not None:
         out["urgent"] = urgent
-    if not args.no_profile:
+    if args.full:
+        # ---- isolated batches (untimed): p50 latency of one call alone, and its per-stage kernel times ----
+        lat = []
+        for _ in range(3):
+            st_iso, l_ms, _ = step()
+            lat.append(l_ms)
+        groups, n_msgs = st_iso.groups, st_iso.unique_messages  # one call alone: its own groups / distinct messages
+        out["config"]["batch_groups_per_step"] = groups
+        out["p50_batch_latency_ms"] = round(float(np.median(lat)), 3)
+    if profile:
         runs = [(list(st.stage_ms[:8]), st.run_sets, st.groups, st.unique_messages // n_dev, miller_k_of(st))
                 for st in runs_timed if n_dev == 1]
         ctx.set_option("profile", 1)
@@ -838,7 +856,7 @@ def main():
         ctx.set_option("profile", 0)
         out["roofline"] = roofline(runs, n_sets // n_dev, groups // n_dev, pk_per_set, value / n_gpus,
                                    miller_k_of(st_p), n_msgs // n_dev, isolated=stage_acc / 2)
-    if rank == 0 and n_gpus == 1 and not (args.no_cpu_baseline and args.no_parity):
+    if args.full and rank == 0 and n_gpus == 1 and not (args.no_cpu_baseline and args.no_parity):
         hc = host_cpus()
         table = oracle_table(work)
         if not args.no_parity:

@@ -6,7 +6,7 @@ TAG=$1
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-A="--gpus 1 --steps 20 --warmup 5"
+A="--full --gpus 1 --steps 20 --warmup 5"  # --full: the roofline and isolated-call legs the trace tools read
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/${TAG}_trace -o run -- python3 $R/bench.py $A --no-cpu-baseline --no-parity > $R/gpurun_out/${TAG}_trace.json 2> $R/gpurun_out/${TAG}_trace.err
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 240 rocprofv3 --pmc $C --output-format csv -d $R/gpurun_out/${TAG}_pmc_$C -o run -- python3 $R/bench.py $A --no-cpu-baseline --no-parity --no-profile > $R/gpurun_out/${TAG}_pmc_$C.log 2>&1
