@@ -14,6 +14,11 @@
  *   blsgpu_destroy                  <- IBlsVerifier.close (chain/bls/interface.ts:45)
  *   blsgpu_aggregate_pubkeys        <- PublicKey.aggregate(pks).toBytes() (chain/bls/utils.ts:5-16,
  *                                      multithread/index.ts:160)
+ *   blsgpu_aggregate_signatures     <- Signature.aggregate(sigs.map(fromBytes)).toBytes(), the op pools' fold of every
+ *                                      verified signature into a running aggregate (beacon-node/src/chain/opPools/
+ *                                      attestationPool.ts, aggregatedAttestationPool.ts, syncCommitteeMessagePool.ts,
+ *                                      syncContributionAndProofPool.ts) and the consensus-spec Aggregate
+ *                                      (beacon-node/test/spec/general/bls.ts `aggregate`)
  *   blsgpu_key_validate             <- PublicKey.fromBytes(pk, CoordType.affine, validate = true) for untrusted
  *                                      keys (state-transition/src/block/processDeposit.ts:56-64,
  *                                      beacon-node/test/spec/general/bls.ts:33-42)
@@ -39,7 +44,7 @@
 extern "C" {
 #endif
 
-#define BLSGPU_ABI_VERSION 7
+#define BLSGPU_ABI_VERSION 8
 
 /* blsgpu_batch.job_flags bits (reference VerifySignatureOpts, chain/bls/interface.ts:3-18) */
 #define BLSGPU_JOB_BATCHABLE 1u /* opts.batchable: the job may share a random-linear-combination group */
@@ -243,6 +248,27 @@ int blsgpu_chunkify(uint32_t len, uint32_t min_per_chunk, uint32_t* chunk_first,
  * identity is encoded as the identity. */
 int blsgpu_aggregate_pubkeys(blsgpu_ctx* ctx, const blsgpu_batch* b, uint8_t* out, uint32_t out_len,
                              int8_t* status);
+
+#define BLSGPU_AGG_VALIDATE 1u /* Signature.fromBytes(.., validate = true): subgroup-check every signature */
+
+/* Signature.aggregate(sigs.map(fromBytes)).toBytes() for n_groups groups at once.  Group g owns signatures
+ * [group_first[g], group_first[g+1]) of sigs[sig_stride * k], each sig_len[k] = 96 (compressed) or 192 bytes;
+ * group_first is [n_groups + 1], non-decreasing, starting at 0 (at most 1 << 20 signatures per call).
+ * out[out_len * g], out_len 96 (compressed) or 192; status[g] = 0, EMPTY_AGGREGATE (no signatures) or the code of
+ * the group's first (lowest-index) rejected signature (INVALID_SIZE, BAD_ENCODING, POINT_NOT_ON_CURVE,
+ * POINT_NOT_IN_GROUP); first_bad[g] (nullable) = that signature's index in the call, 0xffffffff when none.
+ * A rejected group's output is all zero bytes.  A signature that decodes to the identity adds nothing.  A sum equal
+ * to the identity is encoded as the identity (0xc0 / 0x40 then zeros).  Groups never affect each other.
+ * Malformed arguments (a null pointer other than first_bad, out_len, sig_stride < 96, an unknown flag, a group_first
+ * not as above, a 192-byte signature in a narrower stride) return BLSGPU_ERR_ARGS before anything reaches the
+ * device.  Runs on device 0's helper stream, beside verification calls. */
+int blsgpu_aggregate_signatures(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
+                                const uint8_t* sigs, uint32_t sig_stride, const uint32_t* sig_len,
+                                uint32_t flags, uint8_t* out, uint32_t out_len, int8_t* status,
+                                uint32_t* first_bad);
+/* Lanes per group the segmented sum of such a call takes (64 = a wave per group with an LDS tree; 32, 16, 8 = lane
+ * groups with a shuffle butterfly; 1 = a lane per group): non-increasing in n_groups.  Pure host code. */
+uint32_t blsgpu_sig_agg_lanes(uint32_t n_groups, uint32_t n_sigs);
 
 /* KeyValidate of n untrusted pubkeys (pks[stride * i], pk_len 48 compressed or 96 uncompressed): status[i]
  * = 0 or BAD_ENCODING / POINT_NOT_ON_CURVE / PK_IS_INFINITY / POINT_NOT_IN_GROUP; out96 (nullable)

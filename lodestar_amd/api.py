@@ -7,6 +7,8 @@ reference's own functions (same names in snake_case, same argument meaning and e
                                  any error -> False)
 * eth_fast_aggregate_verify      beacon-node/test/spec/general/bls.ts:93-112
 * eth_aggregate_pubkeys          beacon-node/test/spec/general/bls.ts:75-83 (an infinity key -> None)
+* aggregate_signatures           beacon-node/test/spec/general/bls.ts `aggregate` (the consensus-spec Aggregate) and
+                                 the op pools' Signature.aggregate([...]).toBytes() (chain/opPools/*.ts)
 * process_deposit_signature      state-transition/src/block/processDeposit.ts:54-64 (KeyValidate + verify;
                                  any error -> False: the deposit is skipped, not rejected)
 
@@ -114,3 +116,29 @@ def process_deposit_signatures(ctx: Context, pubkeys48, signing_roots, signature
     for k, i in enumerate(ok):
         out[i] = int(res[k]) == 1  # errors (malformed signature) and false both skip the deposit
     return out
+
+
+def aggregate_signature_groups(ctx: Context, groups, validate=True):
+    """Signature.aggregate(group.map(s => Signature.fromBytes(s, validate))).toBytes() for every group of 96- or
+    192-byte signatures in one GPU call: a list with the 96-byte compressed aggregate of each group, or the BlstError
+    the reference throws for it (an empty group: EMPTY_AGGREGATE_ARRAY; else its first rejected signature's)."""
+    groups = [[bytes(s) for s in g] for g in groups]
+    if not groups:
+        return []
+    flat = [s for g in groups for s in g]
+    stride = 192 if any(len(s) > 96 for s in flat) else 96
+    first = np.cumsum([0] + [len(g) for g in groups])
+    # any other length is refused by the device with INVALID_SIZE; its bytes are not read
+    buf = b"".join(s[:stride].ljust(stride, b"\0") for s in flat)
+    out, st, _ = ctx.aggregate_signatures(buf, first, sig_len=[len(s) for s in flat], sig_stride=stride,
+                                          validate=validate)
+    return [out[g] if st[g] == 0 else BlstError(int(st[g])) for g in range(len(groups))]
+
+
+def aggregate_signatures(ctx: Context, signatures, validate=True) -> bytes:
+    """The consensus-spec Aggregate: the 96-byte compressed sum of the signatures.  Raises BlstError for an empty list
+    (EMPTY_AGGREGATE_ARRAY) or a signature Signature.fromBytes rejects."""
+    r = aggregate_signature_groups(ctx, [list(signatures)], validate)[0]
+    if isinstance(r, BlstError):
+        raise r
+    return r

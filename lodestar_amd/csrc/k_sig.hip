@@ -120,8 +120,13 @@ void launch_spec_mask(const PipelineBuffers& b, uint32_t n, uint8_t* spec, hipSt
 }
 
 void launch_sig_decode(const PipelineBuffers& b, uint32_t n, hipStream_t s, bool coop, hipEvent_t decoded,
-                       bool exclusive) {
+                       bool exclusive, bool subgroup) {
   if (!n) return;
+  if (!subgroup) {  // validate = false (k_sigagg.hip): the point decode alone
+    hipLaunchKernelGGL((k_sig_decode<false, BLSGPU_WPE_DEC0>), grid_for(n), dim3(WAVE), 0, s, b, n);
+    if (decoded) (void)hipEventRecord(decoded, s);
+    return;
+  }
   if (coop || BLSGPU_SIG_PAIRS)
     hipLaunchKernelGGL((k_sig_decode<false, BLSGPU_WPE_DEC0>), grid_for(n), dim3(WAVE), 0, s, b, n);
   else

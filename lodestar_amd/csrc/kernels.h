@@ -87,8 +87,9 @@ struct PipelineBuffers {
 // doublings (g2_coop.hpp), for latency; exclusive: each cooperative workgroup takes a CU to itself (small runs only:
 // beyond ~one workgroup per CU the padding serializes the launch)
 // (decoded: recorded after the decode, before the small-run subgroup checks)
+// (subgroup false: Signature.fromBytes(.., validate = false) -- the decode alone, no subgroup-check kernel)
 void launch_sig_decode(const PipelineBuffers& b, uint32_t n_sets, hipStream_t s, bool coop = false,
-                       hipEvent_t decoded = nullptr, bool exclusive = true);
+                       hipEvent_t decoded = nullptr, bool exclusive = true, bool subgroup = true);
 // spec[i] = the signature of set i decoded (the speculative MSM's include mask)
 void launch_spec_mask(const PipelineBuffers& b, uint32_t n_sets, uint8_t* spec, hipStream_t s);
 void launch_hash_prep(const PipelineBuffers& b, hipStream_t s);
@@ -189,6 +190,29 @@ void launch_pk_serialize(const PipelineBuffers& b, uint32_t n_sets, uint8_t* out
 // KeyValidate of untrusted 48/96-byte pubkeys (decode + G1 subgroup check) -> 96-byte uncompressed
 void launch_key_validate(const uint8_t* pks, uint32_t n, uint32_t pk_len, uint32_t stride, uint8_t* out96,
                          int8_t* status, hipStream_t s);
+// Signature.aggregate over groups of decoded signatures (k_sigagg.hip; b fills sig_aff, flags, status and n as
+// launch_sig_decode left them): group g sums signatures [group_first[g], group_first[g+1]) into agg (W_G2J SoA,
+// stride n_groups), agg_status[g] / first_bad[g] = the code and index of its first rejected signature (0 / 0xffffffff).
+// Lanes per group, by group count and mean group size: a wave per group (64, LDS tree) while that leaves SIMDs idle
+// (<= 1,024 groups), then the fewest lanes of 32, 16, 8 (shuffle butterfly) that still give every SIMD a wave
+// (n_groups * L >= 65,536 lanes), then one lane per group; never more lanes than the next form above the mean group
+// size, and one lane for groups of up to three signatures (the pool insert: a butterfly level costs a full Jacobian
+// addition, more than the serial mixed additions it saves).  Non-increasing in n_groups for a given n_sigs.
+inline uint32_t sig_agg_lanes(uint32_t n_groups, uint32_t n_sigs) {
+  if (n_groups == 0) return 1;
+  const uint64_t n = n_groups, lanes = 1024 * 64;
+  const uint32_t by_count = n * 64 <= lanes ? 64 : n * 32 <= 2 * lanes ? 32 : n * 16 <= 2 * lanes ? 16
+                            : n * 8 <= 2 * lanes ? 8 : 1;
+  const uint64_t mean = ((uint64_t)n_sigs + n - 1) / n;
+  const uint32_t by_size = mean <= 3 ? 1 : mean <= 8 ? 8 : mean <= 16 ? 16 : mean <= 32 ? 32 : 64;
+  return by_count < by_size ? by_count : by_size;
+}
+void launch_sig_aggregate(const PipelineBuffers& b, const uint32_t* group_first, uint32_t n_groups, uint32_t n_sigs,
+                          uint32_t* agg, int8_t* agg_status, uint32_t* first_bad, hipStream_t s);
+// Signature.toBytes() of the sums: out[out_len * g], out_len 96 (compressed) or 192; zeros for a rejected or empty
+// group; agg_status[g] becomes the group's status (EMPTY_AGGREGATE for an empty group)
+void launch_sig_agg_serialize(const uint32_t* group_first, uint32_t n_groups, const uint32_t* agg, int8_t* agg_status,
+                              uint8_t* out, uint32_t out_len, hipStream_t s);
 // SSZ signing roots (SigningData / AttestationData hash_tree_root)
 void launch_signing_roots(int kind, const uint8_t* in, uint32_t n, uint32_t in_stride, const uint8_t* domain,
                           uint32_t domain_stride, uint8_t* out, hipStream_t s);

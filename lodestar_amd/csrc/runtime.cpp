@@ -3097,6 +3097,72 @@ int blsgpu_aggregate_pubkeys(blsgpu_ctx* ctx, const blsgpu_batch* b, uint8_t* ou
   return rc;
 }
 
+int blsgpu_aggregate_signatures(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
+                                const uint8_t* sigs, uint32_t sig_stride, const uint32_t* sig_len, uint32_t flags,
+                                uint8_t* out, uint32_t out_len, int8_t* status, uint32_t* first_bad) {
+  if (!ctx || ctx->devs.empty() || !group_first || !sigs || !sig_len || !out || !status) return BLSGPU_ERR_ARGS;
+  if ((out_len != 96 && out_len != 192) || sig_stride < 96 || (flags & ~BLSGPU_AGG_VALIDATE)) return BLSGPU_ERR_ARGS;
+  if (n_groups == 0) return BLSGPU_OK;
+  if (group_first[0] != 0) return BLSGPU_ERR_ARGS;
+  for (uint32_t g = 0; g < n_groups; g++)
+    if (group_first[g + 1] < group_first[g]) return BLSGPU_ERR_ARGS;
+  const uint32_t n = group_first[n_groups], G = n_groups;
+  if (n > (1u << 20)) return BLSGPU_ERR_ARGS;
+  if (sig_stride < 192)
+    for (uint32_t k = 0; k < n; k++)
+      if (sig_len[k] == 192) return BLSGPU_ERR_ARGS;
+  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
+  Device* d = ctx->devs[0];
+  int rc = BLSGPU_OK;
+  try {
+    std::lock_guard<std::mutex> hl(d->helper_mu);
+    HIPCHK(hipSetDevice(d->id));
+    // group_first | sig_len | sigs | out | first_bad | group status | signature status | signature flags
+    const size_t o_len = al256((size_t)(G + 1) * 4), o_sigs = al256(o_len + (size_t)n * 4),
+                 o_out = al256(o_sigs + (size_t)n * sig_stride), o_fb = al256(o_out + (size_t)G * out_len),
+                 o_gst = al256(o_fb + (size_t)G * 4), o_st = al256(o_gst + G), o_fl = al256(o_st + n),
+                 total = o_fl + n;
+    Slot& sl = d->helper;
+    sl.d_in.ensure(total);
+    sl.d_work.ensure((size_t)n * W_G2A + (size_t)G * W_G2J);
+    hipStream_t s = d->table_stream;
+    uint8_t* din = sl.d_in.p;
+    HIPCHK(hipMemcpyAsync(din, group_first, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
+    if (n) {
+      HIPCHK(hipMemcpyAsync(din + o_len, sig_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(din + o_sigs, sigs, (size_t)n * sig_stride, hipMemcpyHostToDevice, s));
+    }
+    PipelineBuffers pb;
+    memset(&pb, 0, sizeof pb);
+    pb.n = n;
+    pb.sigs = din + o_sigs;
+    pb.sig_len = reinterpret_cast<uint32_t*>(din + o_len);
+    pb.sig_stride = sig_stride;
+    pb.sig_aff = sl.d_work.p;
+    pb.flags = din + o_fl;
+    pb.status = reinterpret_cast<int8_t*>(din + o_st);
+    const uint32_t* d_first = reinterpret_cast<uint32_t*>(din);
+    uint32_t* agg = sl.d_work.p + (size_t)n * W_G2A;
+    int8_t* d_gst = reinterpret_cast<int8_t*>(din + o_gst);
+    uint32_t* d_fb = reinterpret_cast<uint32_t*>(din + o_fb);
+    // small calls (the pool insert) take the cooperative subgroup check, as small verification runs do
+    launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, (flags & BLSGPU_AGG_VALIDATE) != 0);
+    launch_sig_aggregate(pb, d_first, G, n, agg, d_gst, d_fb, s);
+    launch_sig_agg_serialize(d_first, G, agg, d_gst, din + o_out, out_len, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, din + o_out, (size_t)G * out_len, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, din + o_gst, G, hipMemcpyDeviceToHost, s));
+    if (first_bad) HIPCHK(hipMemcpyAsync(first_bad, din + o_fb, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  } catch (HipError&) {
+    rc = BLSGPU_DEVICE_ERROR;
+  }
+  leave(ctx);
+  return rc;
+}
+
+uint32_t blsgpu_sig_agg_lanes(uint32_t n_groups, uint32_t n_sigs) { return sig_agg_lanes(n_groups, n_sigs); }
+
 int blsgpu_key_validate(blsgpu_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_t pk_len, uint32_t stride,
                         uint8_t* out96, int8_t* status) {
   if (!ctx || ctx->devs.empty() || !pks || !status || stride < pk_len) return BLSGPU_ERR_ARGS;

@@ -25,6 +25,9 @@ ERR_ENTROPY = 103
 # blsgpu_batch.job_flags bits
 JOB_BATCHABLE = 1
 JOB_URGENT = 2  # VerifySignatureOpts.verifyOnMainThread: the device's urgent lane
+# blsgpu_aggregate_signatures flags
+AGG_VALIDATE = 1  # Signature.fromBytes(.., validate = true)
+AGG_MAX_SIGS = 1 << 20
 # blsgpu_debug_inject targets
 INJECT_ENTROPY = 1
 INJECT_DEVICE = 2
@@ -49,6 +52,8 @@ EXPORTED_SYMBOLS = [
     "blsgpu_batch_scalars",
     "blsgpu_debug_inject",
     "blsgpu_route_call",
+    "blsgpu_aggregate_signatures",
+    "blsgpu_sig_agg_lanes",
 ]
 ROOT_OBJECT = 0
 ROOT_ATTESTATION_DATA = 1
@@ -154,6 +159,10 @@ def load():
     lib.blsgpu_debug_inject.restype = ctypes.c_int
     lib.blsgpu_route_call.argtypes = [u32, u32, vp, ctypes.c_int64, u32, vp, vp]
     lib.blsgpu_route_call.restype = ctypes.c_int
+    lib.blsgpu_aggregate_signatures.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, vp]
+    lib.blsgpu_aggregate_signatures.restype = ctypes.c_int
+    lib.blsgpu_sig_agg_lanes.argtypes = [u32, u32]
+    lib.blsgpu_sig_agg_lanes.restype = u32
     _lib = lib
     return lib
 
@@ -186,6 +195,41 @@ def route_call(n_sets, device_load, split_sets=16384, start=0):
     if rc != OK:
         raise ValueError(f"blsgpu_route_call -> {code_name(rc)}")
     return [int(x) for x in out[: k.value]]
+
+
+def sig_agg_lanes(n_groups, n_sigs):
+    """Lanes per group blsgpu_aggregate_signatures gives a call of this shape (C-ABI blsgpu_sig_agg_lanes, pure host
+    code): 64, 32, 16, 8 or 1."""
+    return int(load().blsgpu_sig_agg_lanes(n_groups, n_sigs))
+
+
+def aggregate_layout(sigs, group_first, sig_len=None, sig_stride=None, out_len=96):
+    """The arrays of one blsgpu_aggregate_signatures call, checked on the host: (sigs uint8, group_first uint32,
+    sig_len uint32, sig_stride).  Raises ValueError for a layout the library would refuse."""
+    gf = np.ascontiguousarray(group_first, dtype=np.int64)
+    if gf.ndim != 1 or len(gf) == 0:
+        raise ValueError("group_first needs n_groups + 1 >= 1 entries")
+    if gf[0] != 0 or (np.diff(gf) < 0).any():
+        raise ValueError("group_first must start at 0 and never decrease")
+    n = int(gf[-1])
+    if n > AGG_MAX_SIGS:
+        raise ValueError(f"at most {AGG_MAX_SIGS} signatures per call")
+    if out_len not in (96, 192):
+        raise ValueError("out_len must be 96 or 192")
+    buf = _u8(sigs)
+    if sig_stride is None:
+        sig_stride = (len(buf) // n) if n else 96
+    if sig_stride < 96:
+        raise ValueError("sig_stride must be at least 96")
+    if len(buf) < n * sig_stride:
+        raise ValueError(f"{n} signatures of stride {sig_stride} need {n * sig_stride} bytes, got {len(buf)}")
+    sl = np.full(n, sig_stride if sig_stride in (96, 192) else 96, np.uint32) if sig_len is None else \
+        np.ascontiguousarray(sig_len, dtype=np.uint32)
+    if sl.ndim != 1 or len(sl) != n:
+        raise ValueError(f"sig_len needs one entry per signature ({n})")
+    if sig_stride < 192 and (sl == 192).any():
+        raise ValueError("a 192-byte signature needs sig_stride >= 192")
+    return buf, gf.astype(np.uint32), sl, int(sig_stride)
 
 
 def chunkify(length, min_per_chunk):
@@ -390,6 +434,27 @@ class Context:
         if rc != OK:
             raise RuntimeError(f"blsgpu_aggregate_pubkeys -> {code_name(rc)}")
         return [out[out_len * i: out_len * (i + 1)].tobytes() for i in range(n)], st[:n]
+
+    def aggregate_signatures(self, sigs, group_first, sig_len=None, sig_stride=None, validate=True, out_len=96):
+        """Signature.aggregate(sigs.map(fromBytes)).toBytes() per group on the GPU.  Group g owns signatures
+        [group_first[g], group_first[g + 1]) of sigs[sig_stride * k] (sig_len[k] bytes each; default: all sig_stride).
+        Returns (list of out_len-byte encodings, status int8 array, first_bad uint32 array); a rejected or empty group
+        gives zero bytes.  ValueError for a malformed layout, before the library is called."""
+        buf, gf, sl, stride = aggregate_layout(sigs, group_first, sig_len, sig_stride, out_len)
+        n = len(gf) - 1
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        if len(sl) == 0:
+            sl = np.zeros(1, np.uint32)
+        out = np.zeros(max(n, 1) * out_len, np.uint8)
+        st = np.zeros(max(n, 1), np.int8)
+        fb = np.full(max(n, 1), 0xFFFFFFFF, np.uint32)
+        rc = self._lib.blsgpu_aggregate_signatures(self.h, n, gf.ctypes.data, buf.ctypes.data, stride, sl.ctypes.data,
+                                                   AGG_VALIDATE if validate else 0, out.ctypes.data, out_len,
+                                                   st.ctypes.data, fb.ctypes.data)
+        if rc != OK:
+            raise RuntimeError(f"blsgpu_aggregate_signatures -> {code_name(rc)}")
+        return [out[out_len * i: out_len * (i + 1)].tobytes() for i in range(n)], st[:n], fb[:n]
 
     def key_validate(self, pks: bytes, pk_len: int):
         """KeyValidate on the GPU: (96-byte uncompressed keys, status int8 array)."""

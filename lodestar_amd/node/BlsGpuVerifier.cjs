@@ -171,6 +171,52 @@ class BlsGpuVerifier {
     return code === 1;
   }
 
+  /**
+   * Signature.aggregate(group.map((s) => Signature.fromBytes(s, validate))).toBytes() for every group in one device
+   * call: what the op pools do per inserted signature (chain/opPools/attestationPool.ts, aggregatedAttestationPool.ts,
+   * syncCommitteeMessagePool.ts, syncContributionAndProofPool.ts), off the main thread (the addon runs the call on a
+   * libuv worker).  Resolves to one entry per group: the aggregate's bytes (96 compressed, or 192 with
+   * {compressed: false}), or -- for a rejected group -- the Error the reference throws for it ("BLST_ERROR: <NAME>"
+   * of its first rejected signature, "EMPTY_AGGREGATE_ARRAY" for an empty group).  Rejects only for a call-level
+   * failure or a closed verifier (QUEUE_ERROR_QUEUE_ABORTED).
+   * @param {Uint8Array[][]} groups
+   * @param {{validate?: boolean, compressed?: boolean}} opts
+   * @returns {Promise<Array<Uint8Array | Error>>}
+   */
+  async aggregateSignatures(groups, {validate = true, compressed = true} = {}) {
+    if (this.closed) throw new QueueError({code: QUEUE_ABORTED});
+    let n = 0;
+    let stride = 96;
+    for (const g of groups)
+      for (const s of g) {
+        n++;
+        if (s.length > 96) stride = SIG_STRIDE;
+      }
+    const groupFirst = new Uint32Array(groups.length + 1);
+    const sigs = new Uint8Array(stride * n);
+    const sigLen = new Uint32Array(n);
+    let k = 0;
+    groups.forEach((g, gi) => {
+      groupFirst[gi] = k;
+      for (const s of g) {
+        sigLen[k] = s.length; // 96 / 192, anything else -> BLST_INVALID_SIZE for this group
+        sigs.set(s.subarray(0, Math.min(s.length, stride)), stride * k);
+        k++;
+      }
+    });
+    groupFirst[groups.length] = k;
+    const outLen = compressed ? 96 : SIG_STRIDE;
+    const p = addon.aggregateSignatures(this.ctx, sigs, sigLen, stride, groupFirst, validate, outLen).then(
+      (r) => groups.map((_, gi) => (r.status[gi] === 0 ? r.out.slice(outLen * gi, outLen * (gi + 1)) : jobError(r.status[gi]))),
+      (err) => {
+        throw err.code === QUEUE_ABORTED ? new QueueError({code: QUEUE_ABORTED}) : err;
+      }
+    );
+    this.inflight.add(p);
+    p.finally(() => this.inflight.delete(p)).catch(() => {});
+    return p;
+  }
+
   /** IBlsVerifier.close (interface.ts:45). */
   async close() {
     if (this.closed) return;
@@ -185,7 +231,7 @@ class BlsGpuVerifier {
     this.queuedTimer = null;
     pending.push(...this.queued.splice(0, this.queued.length));
     for (const job of pending) job.reject(new QueueError({code: QUEUE_ABORTED}));
-    // in-flight submissions complete (the device finishes them) before the context is freed
+    // in-flight submissions and aggregation calls complete (the device finishes them) before the context is freed
     await Promise.allSettled(Array.from(this.inflight));
     addon.close(this.ctx);
   }

@@ -23,6 +23,11 @@
  *     (pkBytes alone: one 96-B key per set; pkBytes + setPkFirst: bytes-aggregate; setPkFirst + pkIndex:
  *      device table)
  *   keyValidate(ctx, Uint8Array, pkLen) -> {pk96, status}        blsgpu_key_validate (synchronous)
+ *   aggregateSignatures(ctx, sigs: Uint8Array, sigLen: Uint32Array, sigStride, groupFirst: Uint32Array, validate,
+ *                       outLen 96|192) -> Promise<{out: Uint8Array, status: Int8Array, firstBad: Uint32Array}>
+ *     blsgpu_aggregate_signatures as napi_create_async_work: the inputs are copied before it returns, the C call
+ *     runs on a libuv worker thread and the promise settles on the main thread (the event loop is never blocked).
+ *     close(ctx) throws while such calls are outstanding: the JS class waits for them first.
  *   debugInject(what, skip, count)                                blsgpu_debug_inject (only with BLSGPU_FAULT_INJECTION=1)
  */
 #define NAPI_VERSION 6
@@ -44,6 +49,7 @@
 
 typedef struct {
   blsgpu_ctx* ctx;
+  uint32_t agg_pending; /* aggregateSignatures calls queued or running (main thread only) */
 } CtxBox;
 
 typedef struct {
@@ -126,6 +132,11 @@ static napi_value Close(napi_env env, napi_callback_info info) {
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   CtxBox* box = get_box(env, argv[0]);
   if (!box) return NULL;
+  if (box->ctx && box->agg_pending) {
+    /* a queued worker still holds the context: destroying it now would free it under that call */
+    napi_throw_error(env, "BLSGPU_ERR_ARGS", "close: aggregateSignatures calls are outstanding");
+    return NULL;
+  }
   if (box->ctx) {
     /* waits for in-flight submissions (their callbacks are queued on the tsfn), fails queued ones */
     blsgpu_destroy(box->ctx);
@@ -418,6 +429,145 @@ static napi_value KeyValidate(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* aggregateSignatures: one blsgpu_aggregate_signatures call as async work */
+typedef struct {
+  CtxBox* box;
+  uint32_t n_groups, stride, flags, out_len;
+  uint32_t* group_first;
+  uint32_t* sig_len;
+  uint8_t* sigs;
+  uint8_t* out;
+  int8_t* status;
+  uint32_t* first_bad;
+  int rc;
+  napi_deferred deferred;
+  napi_async_work work;
+} AggCall;
+
+static void agg_free(AggCall* a) {
+  free(a->group_first);
+  free(a->sig_len);
+  free(a->sigs);
+  free(a->out);
+  free(a->status);
+  free(a->first_bad);
+  free(a);
+}
+
+/* libuv worker thread */
+static void agg_execute(napi_env env, void* data) {
+  (void)env;
+  AggCall* a = (AggCall*)data;
+  a->rc = blsgpu_aggregate_signatures(a->box->ctx, a->n_groups, a->group_first, a->sigs, a->stride, a->sig_len,
+                                      a->flags, a->out, a->out_len, a->status, a->first_bad);
+}
+
+static napi_value copy_out(napi_env env, napi_typedarray_type type, const void* src, size_t count, size_t elem) {
+  napi_value ab, arr;
+  void* dst = NULL;
+  napi_create_arraybuffer(env, count * elem, &dst, &ab);
+  if (count) memcpy(dst, src, count * elem);
+  napi_create_typedarray(env, type, count, ab, 0, &arr);
+  return arr;
+}
+
+/* JS main thread */
+static void agg_complete(napi_env env, napi_status st, void* data) {
+  AggCall* a = (AggCall*)data;
+  a->box->agg_pending--;
+  if (st != napi_ok || a->rc != BLSGPU_OK) {
+    const char* name = blsgpu_code_name(st != napi_ok ? BLSGPU_ERR_CLOSED : a->rc);
+    napi_value msg, code, err;
+    napi_create_string_utf8(env, name ? name : "BLSGPU_DEVICE_ERROR", NAPI_AUTO_LENGTH, &msg);
+    napi_create_string_utf8(env, name ? name : "BLSGPU_DEVICE_ERROR", NAPI_AUTO_LENGTH, &code);
+    napi_create_error(env, code, msg, &err);
+    napi_reject_deferred(env, a->deferred, err);
+  } else {
+    napi_value out;
+    napi_create_object(env, &out);
+    napi_set_named_property(env, out, "out", copy_out(env, napi_uint8_array, a->out, (size_t)a->n_groups * a->out_len, 1));
+    napi_set_named_property(env, out, "status", copy_out(env, napi_int8_array, a->status, a->n_groups, 1));
+    napi_set_named_property(env, out, "firstBad", copy_out(env, napi_uint32_array, a->first_bad, a->n_groups, 4));
+    napi_resolve_deferred(env, a->deferred, out);
+  }
+  napi_delete_async_work(env, a->work);
+  agg_free(a);
+}
+
+static void* dup_bytes(const void* src, size_t n) {
+  void* p = malloc(n ? n : 1);
+  if (p && n) memcpy(p, src, n);
+  return p;
+}
+
+static napi_value AggregateSignatures(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 7) {
+    napi_throw_type_error(env, NULL, "aggregateSignatures(ctx, sigs, sigLen, sigStride, groupFirst, validate, outLen)");
+    return NULL;
+  }
+  CtxBox* box = get_open_box(env, argv[0]);
+  if (!box) return NULL;
+  napi_typedarray_type t_sigs, t_len, t_gf;
+  size_t n_bytes = 0, n_len = 0, n_gf = 0;
+  void *sigs = NULL, *slen = NULL, *gf = NULL;
+  if (napi_get_typedarray_info(env, argv[1], &t_sigs, &n_bytes, &sigs, NULL, NULL) != napi_ok ||
+      t_sigs != napi_uint8_array ||
+      napi_get_typedarray_info(env, argv[2], &t_len, &n_len, &slen, NULL, NULL) != napi_ok ||
+      t_len != napi_uint32_array ||
+      napi_get_typedarray_info(env, argv[4], &t_gf, &n_gf, &gf, NULL, NULL) != napi_ok || t_gf != napi_uint32_array) {
+    napi_throw_type_error(env, NULL, "aggregateSignatures: sigs Uint8Array, sigLen and groupFirst Uint32Array expected");
+    return NULL;
+  }
+  uint32_t stride = 0, out_len = 0;
+  bool validate = true;
+  napi_get_value_uint32(env, argv[3], &stride);
+  napi_coerce_to_bool(env, argv[5], &argv[5]);
+  napi_get_value_bool(env, argv[5], &validate);
+  napi_get_value_uint32(env, argv[6], &out_len);
+  /* shape checks on the host before anything is queued */
+  int ok = n_gf >= 1 && stride >= 96 && (out_len == 96 || out_len == 192) && ((const uint32_t*)gf)[0] == 0;
+  for (size_t g = 0; ok && g + 1 < n_gf; g++) ok = ((const uint32_t*)gf)[g + 1] >= ((const uint32_t*)gf)[g];
+  ok = ok && ((const uint32_t*)gf)[n_gf - 1] == n_len && n_len <= (1u << 20) && n_bytes >= (size_t)stride * n_len;
+  for (size_t k = 0; ok && stride < 192 && k < n_len; k++) ok = ((const uint32_t*)slen)[k] != 192;
+  if (!ok) {
+    napi_throw_range_error(env, "BLSGPU_ERR_ARGS", "aggregateSignatures: inconsistent array sizes");
+    return NULL;
+  }
+  AggCall* a = (AggCall*)calloc(1, sizeof(AggCall));
+  a->box = box;
+  a->n_groups = (uint32_t)n_gf - 1;
+  a->stride = stride;
+  a->flags = validate ? BLSGPU_AGG_VALIDATE : 0;
+  a->out_len = out_len;
+  a->group_first = (uint32_t*)dup_bytes(gf, n_gf * 4);
+  a->sig_len = (uint32_t*)dup_bytes(slen, n_len * 4);
+  a->sigs = (uint8_t*)dup_bytes(sigs, (size_t)stride * n_len);
+  a->out = (uint8_t*)calloc((size_t)a->n_groups * out_len + 1, 1);
+  a->status = (int8_t*)calloc((size_t)a->n_groups + 1, 1);
+  a->first_bad = (uint32_t*)calloc((size_t)a->n_groups + 1, 4);
+  napi_value promise, name;
+  if (!a->group_first || !a->sig_len || !a->sigs || !a->out || !a->status || !a->first_bad ||
+      napi_create_promise(env, &a->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "blsgpu_aggregate_signatures", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, NULL, name, agg_execute, agg_complete, a, &a->work) != napi_ok) {
+    agg_free(a);
+    napi_throw_error(env, NULL, "aggregateSignatures: could not queue the call");
+    return NULL;
+  }
+  box->agg_pending++;
+  if (napi_queue_async_work(env, a->work) != napi_ok) {
+    box->agg_pending--;
+    napi_delete_async_work(env, a->work);
+    agg_free(a);
+    napi_throw_error(env, NULL, "aggregateSignatures: could not queue the call");
+    return NULL;
+  }
+  return promise;
+}
+
 /* debugInject(what, skip, count): blsgpu_debug_inject (test hook; BLSGPU_INJECT_ENTROPY 1, BLSGPU_INJECT_DEVICE 2) */
 static napi_value DebugInject(napi_env env, napi_callback_info info) {
   size_t argc = 3;
@@ -449,6 +599,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
       {"codeName", NULL, CodeName, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"submit", NULL, Submit, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"keyValidate", NULL, KeyValidate, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
+      {"aggregateSignatures", NULL, AggregateSignatures, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   /* the fault-injection test hook is exported, by its own definition, only to processes started with

@@ -35,7 +35,16 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
   /** IBlsVerifier.verifySignatureSets: true iff every set verifies; rejects with "BLST_ERROR: <CODE>" where the
    * reference's Signature.fromBytes throws, "QUEUE_ERROR_QUEUE_ABORTED" once closed. */
   verifySignatureSets(sets: ISignatureSet[], opts?: VerifySignatureOpts): Promise<boolean>;
-  /** IBlsVerifier.close: rejects buffered jobs with QUEUE_ERROR_QUEUE_ABORTED, then frees the devices. */
+  /** Signature.aggregate(group.map(fromBytes)).toBytes() for every group in one device call, off the main thread (the
+   * op pools' fold, chain/opPools/*.ts).  One entry per group: the aggregate (96 bytes compressed, 192 with
+   * compressed: false) or, for a rejected group, the Error the reference throws ("BLST_ERROR: <NAME>",
+   * "EMPTY_AGGREGATE_ARRAY").  Rejects only for a call-level failure or once closed (QUEUE_ERROR_QUEUE_ABORTED). */
+  aggregateSignatures(
+    groups: Uint8Array[][],
+    opts?: {validate?: boolean; compressed?: boolean}
+  ): Promise<Array<Uint8Array | Error>>;
+  /** IBlsVerifier.close: rejects buffered jobs with QUEUE_ERROR_QUEUE_ABORTED, waits for in-flight submissions and
+   * aggregation calls, then frees the devices. */
   close(): Promise<void>;
   /** index2pubkey sync: entries [firstIndex, firstIndex + n) as 96-byte uncompressed encodings. */
   uploadPubkeys(firstIndex: number, pk96: Uint8Array): void;
