@@ -19,6 +19,12 @@
  *                                      attestationPool.ts, aggregatedAttestationPool.ts, syncCommitteeMessagePool.ts,
  *                                      syncContributionAndProofPool.ts) and the consensus-spec Aggregate
  *                                      (beacon-node/test/spec/general/bls.ts `aggregate`)
+ *   blsgpu_aggregate_with_randomness <- blst-ts aggregateWithRandomness(sets): Signature.fromBytes(sig, validate = true)
+ *                                      per set, a fresh 64-bit scalar r_i per set, P = sum r_i pk_i, S = sum r_i sig_i;
+ *                                      the first step of IBlsVerifier.verifySignatureSetsSameMessage (chain/bls/
+ *                                      multithread/index.ts, jobItem.ts `SameMessage`; gossip attestations sharing one
+ *                                      AttestationData, chain/validation/attestation.ts
+ *                                      validateGossipAttestationsSameAttData)
  *   blsgpu_key_validate             <- PublicKey.fromBytes(pk, CoordType.affine, validate = true) for untrusted
  *                                      keys (state-transition/src/block/processDeposit.ts:56-64,
  *                                      beacon-node/test/spec/general/bls.ts:33-42)
@@ -44,6 +50,8 @@
 extern "C" {
 #endif
 
+/* Bumped when an existing entry point or struct changes.  Entry points added since 8, which leave every existing one
+ * as it was and so keep the number: blsgpu_randomness_words, blsgpu_aggregate_with_randomness, blsgpu_awr_lanes. */
 #define BLSGPU_ABI_VERSION 8
 
 /* blsgpu_batch.job_flags bits (reference VerifySignatureOpts, chain/bls/interface.ts:3-18) */
@@ -270,6 +278,40 @@ int blsgpu_aggregate_signatures(blsgpu_ctx* ctx, uint32_t n_groups, const uint32
  * groups with a shuffle butterfly; 1 = a lane per group): non-increasing in n_groups.  Pure host code. */
 uint32_t blsgpu_sig_agg_lanes(uint32_t n_groups, uint32_t n_sigs);
 
+/* Scalar words of a randomized aggregation: words[k], k < n = 64-bit word k of the call key's ChaCha20 keystream
+ * (block k / 8, words 2 (k % 8) and 2 (k % 8) + 1); never 0.  seed as in blsgpu_batch: 0 = a fresh OS key per call
+ * (BLSGPU_ERR_ENTROPY when the OS gives none), else deterministic.  BLSGPU_ERR_ARGS for a null buffer with n > 0.
+ * Pure host code. */
+int blsgpu_randomness_words(uint32_t n, uint64_t seed, uint64_t* words);
+
+/* aggregateWithRandomness for n_groups groups at once.  Group g owns sets [group_first[g], group_first[g+1]);
+ * group_first is [n_groups + 1], non-decreasing, starting at 0 (at most 1 << 20 sets per call).  Set k's trusted
+ * pubkey is pk_bytes[96 k] (uncompressed affine) or device-table entry pk_index[k]: exactly one of the two pointers
+ * is non-null; a table index beyond the table fails the call with BLSGPU_ERR_ARGS.  Its signature is
+ * sigs[sig_stride * k], sig_len[k] = 96 (compressed) or 192 bytes, always subgroup-checked.  Its scalar is r_k = a +
+ * b lambda of word k of blsgpu_randomness_words(n, seed, ..) (the batch scalar map of blsgpu_debug_op 9 / 10; the
+ * word is never 0, so a one-set group is randomized too, as in blst).  seed 0 draws a fresh OS key per call and
+ * returns BLSGPU_ERR_ENTROPY, with nothing written, when the OS gives none; a non-zero seed gives deterministic words
+ * (comparison runs only).
+ * Per group: out_pk[out_pk_len * g] = P = sum r_k pk_k, out_pk_len 48 (compressed) or 96; out_sig[out_sig_len * g] =
+ * S = sum r_k sig_k, out_sig_len 96 (compressed) or 192.  status[g] = 0, EMPTY_AGGREGATE (no sets) or the code of the
+ * group's lowest-index rejected set: its signature's INVALID_SIZE, BAD_ENCODING, POINT_NOT_ON_CURVE or
+ * POINT_NOT_IN_GROUP, or its bytes-mode key's BAD_ENCODING, POINT_NOT_ON_CURVE or PK_IS_INFINITY (the key's when both
+ * are rejected); first_bad[g] (nullable) = that set's index in the call, 0xffffffff when none.  A rejected or empty
+ * group writes all-zero outputs.  An identity signature contributes nothing to S; its key still contributes to P.  A
+ * sum equal to the identity is encoded as the identity.  Groups never affect each other.
+ * Malformed arguments (a null pointer other than first_bad, both or neither of pk_bytes / pk_index, an output length,
+ * sig_stride < 96, a group_first not as above, a 192-byte signature in a narrower stride) return BLSGPU_ERR_ARGS before
+ * anything reaches the device.  Runs on device 0's helper stream, beside verification calls. */
+int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
+                                     const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
+                                     uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed, uint8_t* out_pk,
+                                     uint32_t out_pk_len, uint8_t* out_sig, uint32_t out_sig_len, int8_t* status,
+                                     uint32_t* first_bad);
+/* Lanes per group the segmented sum of such a call takes (64 = a wave per group with an LDS tree; 32, 16, 8 = lane
+ * groups with a shuffle butterfly; 1 = a lane per group): non-increasing in n_groups.  Pure host code. */
+uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets);
+
 /* KeyValidate of n untrusted pubkeys (pks[stride * i], pk_len 48 compressed or 96 uncompressed): status[i]
  * = 0 or BAD_ENCODING / POINT_NOT_ON_CURVE / PK_IS_INFINITY / POINT_NOT_IN_GROUP; out96 (nullable)
  * receives the uncompressed encoding of every valid key (bytes-mode input of blsgpu_verify). */
@@ -307,7 +349,8 @@ int blsgpu_batch_scalars(const blsgpu_batch* b, uint64_t* words);
 /* Test hook: fault injection, process-wide, available only when the process was started with the environment
  * variable BLSGPU_FAULT_INJECTION=1 (read once; otherwise every call returns BLSGPU_ERR_ARGS and nothing is armed).
  * After `skip` more events, the next `count` events fail:
- *   BLSGPU_INJECT_ENTROPY: an entropy draw (seed-0 calls, blsgpu_batch_scalars) -> BLSGPU_ERR_ENTROPY;
+ *   BLSGPU_INJECT_ENTROPY: an entropy draw (seed-0 calls, blsgpu_batch_scalars, blsgpu_randomness_words) ->
+ *     BLSGPU_ERR_ENTROPY;
  *   BLSGPU_INJECT_DEVICE: a pipeline run, once its batch pass completed, as if a HIP call had failed -> every job
  *     of every call in that run -BLSGPU_DEVICE_ERROR (never 0); the dispatcher keeps serving later calls.
  * count 0 disarms. */

@@ -9,6 +9,10 @@ reference's own functions (same names in snake_case, same argument meaning and e
 * eth_aggregate_pubkeys          beacon-node/test/spec/general/bls.ts:75-83 (an infinity key -> None)
 * aggregate_signatures           beacon-node/test/spec/general/bls.ts `aggregate` (the consensus-spec Aggregate) and
                                  the op pools' Signature.aggregate([...]).toBytes() (chain/opPools/*.ts)
+* aggregate_with_randomness      blst-ts aggregateWithRandomness(sets): {pk, sig} = (sum r_i pk_i, sum r_i sig_i)
+* verify_signature_sets_same_message  IBlsVerifier.verifySignatureSetsSameMessage (chain/bls/interface.ts;
+                                 multithread/index.ts + jobItem.ts: aggregate with randomness, verify the one set,
+                                 retry every set on its own when that fails)
 * process_deposit_signature      state-transition/src/block/processDeposit.ts:54-64 (KeyValidate + verify;
                                  any error -> False: the deposit is skipped, not rejected)
 
@@ -142,3 +146,61 @@ def aggregate_signatures(ctx: Context, signatures, validate=True) -> bytes:
     if isinstance(r, BlstError):
         raise r
     return r
+
+
+def _same_message_arrays(sets):
+    """(pk_bytes or None, pk_index or None, sigs buffer, sig_len, stride) of [(pk96 or table index, sig bytes)]."""
+    sets = [(k, bytes(s)) for k, s in sets]
+    table = [isinstance(k, (int, np.integer)) for k, _ in sets]
+    if any(table) and not all(table):
+        raise ValueError("sets mix table indices and pubkey bytes")
+    stride = 192 if any(len(s) > 96 for _, s in sets) else 96
+    # any other length is refused by the device with INVALID_SIZE; its bytes are not read
+    buf = b"".join(s[:stride].ljust(stride, b"\0") for _, s in sets)
+    sig_len = [len(s) for _, s in sets]
+    if sets and table[0]:
+        return None, np.array([int(k) for k, _ in sets], np.int64), buf, sig_len, stride
+    pks = [bytes(k) for k, _ in sets]
+    if any(len(k) != 96 for k in pks):
+        raise ValueError("96-byte uncompressed pubkeys expected")
+    return b"".join(pks), None, buf, sig_len, stride
+
+
+def aggregate_with_randomness(ctx: Context, sets, seed=0):
+    """blst-ts aggregateWithRandomness(sets) on the GPU, sets = [(pk96 or table index, signature bytes)]: (P, S) =
+    (sum r_i pk_i as 96 bytes uncompressed, sum r_i sig_i as 192 bytes uncompressed) under fresh 64-bit scalars
+    (seed 0), every signature subgroup-checked.  Raises BlstError for an empty list (EMPTY_AGGREGATE_ARRAY) or the
+    first rejected set's error."""
+    sets = list(sets)
+    pkb, pki, buf, sig_len, stride = _same_message_arrays(sets)
+    if not sets:
+        raise BlstError(9)
+    p, s, st, _ = ctx.aggregate_with_randomness([0, len(sets)], buf, pk_bytes=pkb, pk_index=pki, sig_len=sig_len,
+                                                sig_stride=stride, seed=seed)
+    if st[0] != 0:
+        raise BlstError(int(st[0]))
+    return p[0], s[0]
+
+
+def verify_signature_sets_same_message(ctx: Context, sets, message: bytes, seed=0):
+    """IBlsVerifier.verifySignatureSetsSameMessage: sets = [(pk96 or table index, signature bytes)] all signing
+    `message`; a list with one bool per set.  One randomized aggregation, one verification of (P, message, S); when
+    the aggregation rejects a set or that verification is not true, every set is verified on its own (a malformed
+    signature is a False there, not an exception).  Raises BlstError("Empty signature set") for no sets."""
+    sets = list(sets)
+    n = len(sets)
+    if n == 0:
+        raise BlstError(10)
+    message = bytes(message)[:32].ljust(32, b"\0")
+    pkb, pki, buf, sig_len, stride = _same_message_arrays(sets)
+    p, s, st, _ = ctx.aggregate_with_randomness([0, n], buf, pk_bytes=pkb, pk_index=pki, sig_len=sig_len,
+                                                sig_stride=stride, seed=seed)
+    if st[0] == 0:
+        res, _ = ctx.verify_raw([0, 1], s[0], [192], message, pk_bytes=p[0], job_flags=[0], sig_stride=192)
+        if int(res[0]) == 1:
+            return [True] * n
+    # retry: every set as its own one-set job
+    keys = dict(pk_bytes=pkb) if pkb is not None else dict(set_pk_first=np.arange(n + 1), pk_index=pki)
+    res, _ = ctx.verify_raw(np.arange(n + 1), buf, sig_len, message * n, job_flags=np.ones(n), sig_stride=stride,
+                            **keys)
+    return [int(r) == 1 for r in res]

@@ -2,6 +2,7 @@
 // segmented G2 sum over the signatures k_sig_decode left in sig_aff (k_sig.hip), and its serialization.  The G2 twin
 // of k_pk_aggregate / k_pk_aggregate_g / k_pk_serialize (k_pk.hip).
 #include "k_common.hpp"
+#include "seg_sum.hpp"
 
 // One lane's share of group [first, last): signatures first + t, first + t + L, ...  A rejected signature (decode or
 // subgroup status) is the lane's error when it is the lane's first -- k ascends, so that is the lane's lowest index;
@@ -23,13 +24,12 @@ BLS_INL void sig_agg_strided(const PipelineBuffers& b, uint32_t first, uint32_t 
   }
 }
 
-// One wave per group: strided partial sums, then an LDS tree (level s: lanes [s, 2s) hand their sum to lanes [0, s),
-// so WAVE / 2 slots of W_G2J words = 10.5 KB).  The group's first error is the lowest signature index of any lane.
-#define SIGAGG_SLOTS (WAVE / 2)
+// One wave per group: strided partial sums, then the LDS tree of seg_sum.hpp (WAVE / 2 slots of W_G2J words = 10.5
+// KB).  The group's first error is the lowest signature index of any lane.
 __global__ __launch_bounds__(WAVE) void k_sig_aggregate(PipelineBuffers b, const uint32_t* group_first,
                                                         uint32_t n_groups, uint32_t* agg, int8_t* agg_status,
                                                         uint32_t* first_bad) {
-  __shared__ uint32_t red[SIGAGG_SLOTS * W_G2J];
+  __shared__ uint32_t red[SEG_SLOTS * W_G2J];
   __shared__ uint32_t err_k[WAVE];
   __shared__ int32_t err_c[WAVE];
   const uint32_t g = blockIdx.x, lane = threadIdx.x;
@@ -39,56 +39,20 @@ __global__ __launch_bounds__(WAVE) void k_sig_aggregate(PipelineBuffers b, const
   uint32_t my_err_k = 0xffffffffu;
   int my_err = 0;
   sig_agg_strided(b, first, last, lane, WAVE, acc, my_err_k, my_err);
-  err_k[lane] = my_err_k;
-  err_c[lane] = my_err;
-  __syncthreads();
+  uint32_t bk;
+  int bc;
+  seg_wave_first_error(err_k, err_c, lane, my_err_k, my_err, bk, bc);
   if (lane == 0) {
-    uint32_t bk = 0xffffffffu;
-    int bc = 0;
-    for (int l = 0; l < WAVE; l++)
-      if (err_k[l] < bk) {
-        bk = err_k[l];
-        bc = err_c[l];
-      }
     agg_status[g] = (int8_t)bc;
     first_bad[g] = bk;
   }
-  if (last - first > 1) {  // (uniform per workgroup)
-#pragma unroll 1
-    for (int s = WAVE / 2; s >= 1; s >>= 1) {
-      if (lane >= (uint32_t)s && lane < (uint32_t)(2 * s)) {
-        uint32_t* o = red + (lane - s) * W_G2J;
-        const uint32_t* a = reinterpret_cast<const uint32_t*>(&acc);
-#pragma unroll
-        for (int w = 0; w < W_G2J; w++) o[w] = a[w];
-      }
-      __syncthreads();
-      if (lane < (uint32_t)s) {
-        g2j o;
-        uint32_t* d = reinterpret_cast<uint32_t*>(&o);
-        const uint32_t* a = red + lane * W_G2J;
-#pragma unroll
-        for (int w = 0; w < W_G2J; w++) d[w] = a[w];
-        acc = jac_add(acc, o);
-      }
-      __syncthreads();
-    }
-  }
+  if (last - first > 1) seg_wave_tree(acc, red, lane);  // (uniform per workgroup)
   if (lane == 0) st_g2j(agg, n_groups, g, acc);
 }
 
-// The same sum on L lanes per group (64 / L groups per wave; L = 32, 16, 8 or 1), the partial sums combined by an
-// in-register butterfly (__shfl_xor inside the lane group: 84 words per level, no LDS, no barrier).  L = 1 is a lane
-// per group, no butterfly: the one-to-three-signature pool insert.
-BLS_INL fp2 fp2_shfl_xor(const fp2& x, int m) {
-  fp2 r;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) {
-    r.c0.l[i] = (uint32_t)__shfl_xor((int)x.c0.l[i], m);
-    r.c1.l[i] = (uint32_t)__shfl_xor((int)x.c1.l[i], m);
-  }
-  return r;
-}
+// The same sum on L lanes per group (64 / L groups per wave; L = 32, 16, 8 or 1), the partial sums combined by the
+// in-register butterfly of seg_sum.hpp (84 words per level, no LDS, no barrier).  L = 1 is a lane per group, no
+// butterfly: the one-to-three-signature pool insert.
 template <int L>
 __global__ __launch_bounds__(WAVE) void k_sig_aggregate_g(PipelineBuffers b, const uint32_t* group_first,
                                                           uint32_t n_groups, uint32_t* agg, int8_t* agg_status,
@@ -101,21 +65,7 @@ __global__ __launch_bounds__(WAVE) void k_sig_aggregate_g(PipelineBuffers b, con
   uint32_t my_err_k = 0xffffffffu;
   int my_err = 0;
   sig_agg_strided(b, first, last, t, L, acc, my_err_k, my_err);
-  // butterfly: after log2 L levels every lane of the group holds the sum and the first error by signature index
-#pragma unroll 1
-  for (int m = L / 2; m >= 1; m >>= 1) {
-    g2j o;
-    o.x = fp2_shfl_xor(acc.x, m);
-    o.y = fp2_shfl_xor(acc.y, m);
-    o.z = fp2_shfl_xor(acc.z, m);
-    const uint32_t ok = (uint32_t)__shfl_xor((int)my_err_k, m);
-    const int oc = __shfl_xor(my_err, m);
-    if (ok < my_err_k) {
-      my_err_k = ok;
-      my_err = oc;
-    }
-    acc = jac_add(acc, o);
-  }
+  seg_butterfly<fp2, L>(acc, my_err_k, my_err);
   if (on && t == 0) {
     agg_status[g] = (int8_t)my_err;
     first_bad[g] = my_err_k;

@@ -213,6 +213,53 @@ void launch_sig_aggregate(const PipelineBuffers& b, const uint32_t* group_first,
 // group; agg_status[g] becomes the group's status (EMPTY_AGGREGATE for an empty group)
 void launch_sig_agg_serialize(const uint32_t* group_first, uint32_t n_groups, const uint32_t* agg, int8_t* agg_status,
                               uint8_t* out, uint32_t out_len, hipStream_t s);
+// aggregateWithRandomness over groups of sets (k_awr.hip): group g owns sets [group_first[g], group_first[g+1]); per
+// group P = sum r_k pk_k (G1) and S = sum r_k sig_k (G2), r_k the batch scalar of words[k] (never 0).
+struct AwrBuffers {
+  uint32_t n;         // sets; SoA stride of sig_aff
+  uint32_t n_groups;  // SoA stride of sum_pk / sum_sig
+  const uint32_t* group_first;
+  const uint64_t* words;
+  // trusted keys: pk_bytes[96 k] (uncompressed), or table entry pk_index[k] when pk_bytes is null
+  const uint8_t* pk_bytes;
+  const uint32_t* pk_index;
+  const uint32_t* pk_table;
+  uint32_t pk_table_n;
+  // signatures as launch_sig_decode left them
+  const uint32_t* sig_aff;
+  const uint8_t* sig_flags;
+  const int8_t* sig_status;
+  // window scratch: 9 entries of W_G2J words per launched lane (8 window entries laid out as scal_tab, stride tab_n,
+  // and the lane's running sum), shared by the G1 and the G2 kernel
+  uint32_t* tab;
+  uint32_t tab_n;  // launched lanes: awr_launch_lanes(n_groups, L)
+  uint32_t* sum_pk;   // W_G1J per group
+  uint32_t* sum_sig;  // W_G2J per group
+  uint32_t* err_k;    // [2 n_groups]: lowest rejected set index per group (0xffffffff = none), keys then signatures
+  int8_t* err_c;      // [2 n_groups]: its code
+};
+#define AWR_TAB_WORDS (9 * W_G2J)
+// Lanes per group of the segmented randomized sum (blsgpu_awr_lanes).  A set costs two scalar multiplications (~50
+// point operations each), a combine level one Jacobian addition per sum, so -- unlike sig_agg_lanes -- a lane per set
+// pays off from two sets on: the fewest lanes of 8, 16, 32, 64 that cover the mean group size (one lane for one-set
+// groups), capped by the group count: the kernels run one wave per SIMD (the scaling takes the whole register file),
+// so the chip holds 1,024 waves = 65,536 lanes at a time and lanes beyond that only queue: the most lanes of 64, 32,
+// 16, 8 with n_groups * L <= 65,536, then one lane per group.  Non-increasing in n_groups for a given n_sets.
+inline uint32_t awr_lanes(uint32_t n_groups, uint32_t n_sets) {
+  if (n_groups == 0) return 1;
+  const uint64_t n = n_groups, lanes = 1024 * 64;
+  const uint32_t by_count = n * 64 <= lanes ? 64 : n * 32 <= lanes ? 32 : n * 16 <= lanes ? 16 : n * 8 <= lanes ? 8 : 1;
+  const uint64_t mean = ((uint64_t)n_sets + n - 1) / n;
+  const uint32_t by_size = mean <= 1 ? 1 : mean <= 8 ? 8 : mean <= 16 ? 16 : mean <= 32 ? 32 : 64;
+  return by_count < by_size ? by_count : by_size;
+}
+uint32_t awr_launch_lanes(uint32_t n_groups, uint32_t L);
+// sum_pk / sum_sig and the per-group first errors, on L lanes per group (a.tab_n = awr_launch_lanes(n_groups, L))
+void launch_awr_sums(const AwrBuffers& a, uint32_t L, hipStream_t s);
+// both sums' toBytes(): out_pk[out_pk_len * g] (48 compressed / 96), out_sig[out_sig_len * g] (96 compressed / 192),
+// zeros for a rejected or empty group; status[g] / first_bad[g] = the group's status and its rejected set's index
+void launch_awr_serialize(const AwrBuffers& a, uint8_t* out_pk, uint32_t out_pk_len, uint8_t* out_sig,
+                          uint32_t out_sig_len, int8_t* status, uint32_t* first_bad, hipStream_t s);
 // SSZ signing roots (SigningData / AttestationData hash_tree_root)
 void launch_signing_roots(int kind, const uint8_t* in, uint32_t n, uint32_t in_stride, const uint8_t* domain,
                           uint32_t domain_stride, uint8_t* out, hipStream_t s);

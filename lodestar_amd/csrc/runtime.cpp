@@ -3163,6 +3163,129 @@ int blsgpu_aggregate_signatures(blsgpu_ctx* ctx, uint32_t n_groups, const uint32
 
 uint32_t blsgpu_sig_agg_lanes(uint32_t n_groups, uint32_t n_sigs) { return sig_agg_lanes(n_groups, n_sigs); }
 
+int blsgpu_randomness_words(uint32_t n, uint64_t seed, uint64_t* words) {
+  if (n && !words) return BLSGPU_ERR_ARGS;
+  batch_rand::Key key;
+  uint64_t hash_key = 0;
+  if (!resolve_key(seed, key, hash_key)) return BLSGPU_ERR_ENTROPY;
+  batch_rand::words(key, 0, n, words);
+  return BLSGPU_OK;
+}
+
+int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
+                                     const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
+                                     uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed, uint8_t* out_pk,
+                                     uint32_t out_pk_len, uint8_t* out_sig, uint32_t out_sig_len, int8_t* status,
+                                     uint32_t* first_bad) {
+  if (!ctx || ctx->devs.empty() || !group_first || !sigs || !sig_len || !out_pk || !out_sig || !status)
+    return BLSGPU_ERR_ARGS;
+  if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
+  if ((out_pk_len != 48 && out_pk_len != 96) || (out_sig_len != 96 && out_sig_len != 192) || sig_stride < 96)
+    return BLSGPU_ERR_ARGS;
+  if (n_groups == 0) return BLSGPU_OK;
+  if (group_first[0] != 0) return BLSGPU_ERR_ARGS;
+  for (uint32_t g = 0; g < n_groups; g++)
+    if (group_first[g + 1] < group_first[g]) return BLSGPU_ERR_ARGS;
+  const uint32_t n = group_first[n_groups], G = n_groups;
+  if (n > (1u << 20)) return BLSGPU_ERR_ARGS;
+  if (sig_stride < 192)
+    for (uint32_t k = 0; k < n; k++)
+      if (sig_len[k] == 192) return BLSGPU_ERR_ARGS;
+  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
+  // the call's scalars, before anything is written or reaches the device
+  std::vector<uint64_t> words(n);
+  {
+    batch_rand::Key key;
+    uint64_t hash_key = 0;
+    if (!resolve_key(seed, key, hash_key)) {
+      leave(ctx);
+      return BLSGPU_ERR_ENTROPY;
+    }
+    batch_rand::words(key, 0, n, words.data());
+  }
+  Device* d = ctx->devs[0];
+  int rc = BLSGPU_OK;
+  try {
+    std::lock_guard<std::mutex> hl(d->helper_mu);
+    std::shared_lock<std::shared_mutex> tl(d->table_mu);
+    HIPCHK(hipSetDevice(d->id));
+    if (pk_index)
+      for (uint32_t k = 0; k < n; k++)
+        if (pk_index[k] >= d->table_n) rc = BLSGPU_ERR_ARGS;
+    if (rc == BLSGPU_OK) {
+      const uint32_t L = awr_lanes(G, n), lanes = awr_launch_lanes(G, L);
+      // words | group_first | sig_len | sigs | keys | out_pk | out_sig | first_bad | error indices | group status |
+      // error codes | signature status | signature flags
+      const size_t key_bytes = pk_bytes ? (size_t)n * 96 : (size_t)n * 4;
+      const size_t o_gf = al256((size_t)n * 8), o_len = al256(o_gf + (size_t)(G + 1) * 4),
+                   o_sigs = al256(o_len + (size_t)n * 4), o_keys = al256(o_sigs + (size_t)n * sig_stride),
+                   o_opk = al256(o_keys + key_bytes), o_osig = al256(o_opk + (size_t)G * out_pk_len),
+                   o_fb = al256(o_osig + (size_t)G * out_sig_len), o_ek = al256(o_fb + (size_t)G * 4),
+                   o_gst = al256(o_ek + (size_t)G * 8), o_ec = al256(o_gst + G), o_st = al256(o_ec + 2 * (size_t)G),
+                   o_fl = al256(o_st + n), total = o_fl + n;
+      Slot& sl = d->helper;
+      sl.d_in.ensure(total);
+      sl.d_work.ensure((size_t)n * W_G2A + (size_t)lanes * AWR_TAB_WORDS + (size_t)G * (W_G1J + W_G2J));
+      hipStream_t s = d->table_stream;
+      uint8_t* din = sl.d_in.p;
+      HIPCHK(hipMemcpyAsync(din + o_gf, group_first, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
+      if (n) {
+        HIPCHK(hipMemcpyAsync(din, words.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(din + o_len, sig_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(din + o_sigs, sigs, (size_t)n * sig_stride, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(din + o_keys, pk_bytes ? (const void*)pk_bytes : (const void*)pk_index, key_bytes,
+                              hipMemcpyHostToDevice, s));
+      }
+      PipelineBuffers pb;
+      memset(&pb, 0, sizeof pb);
+      pb.n = n;
+      pb.sigs = din + o_sigs;
+      pb.sig_len = reinterpret_cast<uint32_t*>(din + o_len);
+      pb.sig_stride = sig_stride;
+      pb.sig_aff = sl.d_work.p;
+      pb.flags = din + o_fl;
+      pb.status = reinterpret_cast<int8_t*>(din + o_st);
+      AwrBuffers ab;
+      memset(&ab, 0, sizeof ab);
+      ab.n = n;
+      ab.n_groups = G;
+      ab.group_first = reinterpret_cast<uint32_t*>(din + o_gf);
+      ab.words = reinterpret_cast<uint64_t*>(din);
+      ab.pk_bytes = pk_bytes ? din + o_keys : nullptr;
+      ab.pk_index = pk_bytes ? nullptr : reinterpret_cast<uint32_t*>(din + o_keys);
+      ab.pk_table = d->table.p;
+      ab.pk_table_n = d->table_n;
+      ab.sig_aff = pb.sig_aff;
+      ab.sig_flags = pb.flags;
+      ab.sig_status = pb.status;
+      ab.tab = sl.d_work.p + (size_t)n * W_G2A;
+      ab.tab_n = lanes;
+      ab.sum_pk = ab.tab + (size_t)lanes * AWR_TAB_WORDS;
+      ab.sum_sig = ab.sum_pk + (size_t)G * W_G1J;
+      ab.err_k = reinterpret_cast<uint32_t*>(din + o_ek);
+      ab.err_c = reinterpret_cast<int8_t*>(din + o_ec);
+      int8_t* d_gst = reinterpret_cast<int8_t*>(din + o_gst);
+      uint32_t* d_fb = reinterpret_cast<uint32_t*>(din + o_fb);
+      // small calls take the cooperative subgroup check, as small verification runs do
+      launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, true);
+      launch_awr_sums(ab, L, s);
+      launch_awr_serialize(ab, din + o_opk, out_pk_len, din + o_osig, out_sig_len, d_gst, d_fb, s);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(out_pk, din + o_opk, (size_t)G * out_pk_len, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(out_sig, din + o_osig, (size_t)G * out_sig_len, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(status, din + o_gst, G, hipMemcpyDeviceToHost, s));
+      if (first_bad) HIPCHK(hipMemcpyAsync(first_bad, din + o_fb, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+    }
+  } catch (HipError&) {
+    rc = BLSGPU_DEVICE_ERROR;
+  }
+  leave(ctx);
+  return rc;
+}
+
+uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets) { return awr_lanes(n_groups, n_sets); }
+
 int blsgpu_key_validate(blsgpu_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_t pk_len, uint32_t stride,
                         uint8_t* out96, int8_t* status) {
   if (!ctx || ctx->devs.empty() || !pks || !status || stride < pk_len) return BLSGPU_ERR_ARGS;

@@ -54,6 +54,9 @@ EXPORTED_SYMBOLS = [
     "blsgpu_route_call",
     "blsgpu_aggregate_signatures",
     "blsgpu_sig_agg_lanes",
+    "blsgpu_randomness_words",
+    "blsgpu_aggregate_with_randomness",
+    "blsgpu_awr_lanes",
 ]
 ROOT_OBJECT = 0
 ROOT_ATTESTATION_DATA = 1
@@ -163,6 +166,13 @@ def load():
     lib.blsgpu_aggregate_signatures.restype = ctypes.c_int
     lib.blsgpu_sig_agg_lanes.argtypes = [u32, u32]
     lib.blsgpu_sig_agg_lanes.restype = u32
+    lib.blsgpu_randomness_words.argtypes = [u32, ctypes.c_uint64, vp]
+    lib.blsgpu_randomness_words.restype = ctypes.c_int
+    lib.blsgpu_aggregate_with_randomness.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, ctypes.c_uint64, vp, u32, vp,
+                                                     u32, vp, vp]
+    lib.blsgpu_aggregate_with_randomness.restype = ctypes.c_int
+    lib.blsgpu_awr_lanes.argtypes = [u32, u32]
+    lib.blsgpu_awr_lanes.restype = u32
     _lib = lib
     return lib
 
@@ -230,6 +240,48 @@ def aggregate_layout(sigs, group_first, sig_len=None, sig_stride=None, out_len=9
     if sig_stride < 192 and (sl == 192).any():
         raise ValueError("a 192-byte signature needs sig_stride >= 192")
     return buf, gf.astype(np.uint32), sl, int(sig_stride)
+
+
+def awr_lanes(n_groups, n_sets):
+    """Lanes per group blsgpu_aggregate_with_randomness gives a call of this shape (C-ABI blsgpu_awr_lanes, pure host
+    code): 64, 32, 16, 8 or 1."""
+    return int(load().blsgpu_awr_lanes(n_groups, n_sets))
+
+
+def randomness_words(n, seed):
+    """The scalar words of a randomized aggregation of n sets (C-ABI blsgpu_randomness_words, pure host code): a
+    uint64 array, never 0; seed 0 draws a fresh key per call.  RuntimeError when the OS gives no randomness."""
+    out = np.zeros(max(n, 1), np.uint64)
+    rc = load().blsgpu_randomness_words(n, seed, out.ctypes.data)
+    if rc != OK:
+        raise RuntimeError(f"blsgpu_randomness_words -> {code_name(rc)}")
+    return out[:n]
+
+
+def awr_layout(group_first, sigs, pk_bytes=None, pk_index=None, sig_len=None, sig_stride=None, out_pk_len=96,
+               out_sig_len=192):
+    """The arrays of one blsgpu_aggregate_with_randomness call, checked on the host: (group_first uint32, sigs uint8,
+    sig_len uint32, sig_stride, pk_bytes uint8 or None, pk_index uint32 or None).  Raises ValueError for a layout the
+    library would refuse."""
+    if out_pk_len not in (48, 96):
+        raise ValueError("out_pk_len must be 48 or 96")
+    buf, gf, sl, stride = aggregate_layout(sigs, group_first, sig_len, sig_stride, out_sig_len)
+    n = int(gf[-1])
+    if (pk_bytes is None) == (pk_index is None):
+        raise ValueError("exactly one of pk_bytes and pk_index")
+    pkb = pki = None
+    if pk_bytes is not None:
+        pkb = _u8(pk_bytes)
+        if len(pkb) != 96 * n:
+            raise ValueError(f"{n} sets need {96 * n} pubkey bytes, got {len(pkb)}")
+    else:
+        idx = np.ascontiguousarray(pk_index, dtype=np.int64)
+        if idx.ndim != 1 or len(idx) != n:
+            raise ValueError(f"pk_index needs one entry per set ({n})")
+        if n and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+            raise ValueError("pk_index entries must be table indices")
+        pki = idx.astype(np.uint32)
+    return gf, buf, sl, stride, pkb, pki
 
 
 def chunkify(length, min_per_chunk):
@@ -455,6 +507,37 @@ class Context:
         if rc != OK:
             raise RuntimeError(f"blsgpu_aggregate_signatures -> {code_name(rc)}")
         return [out[out_len * i: out_len * (i + 1)].tobytes() for i in range(n)], st[:n], fb[:n]
+
+    def aggregate_with_randomness(self, group_first, sigs, pk_bytes=None, pk_index=None, sig_len=None,
+                                  sig_stride=None, seed=0, out_pk_len=96, out_sig_len=192):
+        """blst aggregateWithRandomness per group on the GPU: group g owns sets [group_first[g], group_first[g + 1]),
+        set k = (pk_bytes[96 k] or table entry pk_index[k], sigs[sig_stride * k] of sig_len[k] bytes).  Returns (list
+        of P encodings, list of S encodings, status int8 array, first_bad uint32 array); a rejected or empty group
+        gives zero bytes.  seed 0 = fresh scalars (production); else the words of randomness_words(n, seed).
+        ValueError for a malformed layout, before the library is called."""
+        gf, buf, sl, stride, pkb, pki = awr_layout(group_first, sigs, pk_bytes, pk_index, sig_len, sig_stride,
+                                                   out_pk_len, out_sig_len)
+        n = len(gf) - 1
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        if len(sl) == 0:
+            sl = np.zeros(1, np.uint32)
+        if pkb is not None and len(pkb) == 0:
+            pkb = np.zeros(1, np.uint8)
+        if pki is not None and len(pki) == 0:
+            pki = np.zeros(1, np.uint32)
+        opk = np.zeros(max(n, 1) * out_pk_len, np.uint8)
+        osig = np.zeros(max(n, 1) * out_sig_len, np.uint8)
+        st = np.zeros(max(n, 1), np.int8)
+        fb = np.full(max(n, 1), 0xFFFFFFFF, np.uint32)
+        rc = self._lib.blsgpu_aggregate_with_randomness(
+            self.h, n, gf.ctypes.data, None if pkb is None else pkb.ctypes.data,
+            None if pki is None else pki.ctypes.data, buf.ctypes.data, stride, sl.ctypes.data, seed, opk.ctypes.data,
+            out_pk_len, osig.ctypes.data, out_sig_len, st.ctypes.data, fb.ctypes.data)
+        if rc != OK:
+            raise RuntimeError(f"blsgpu_aggregate_with_randomness -> {code_name(rc)}")
+        return ([opk[out_pk_len * i: out_pk_len * (i + 1)].tobytes() for i in range(n)],
+                [osig[out_sig_len * i: out_sig_len * (i + 1)].tobytes() for i in range(n)], st[:n], fb[:n])
 
     def key_validate(self, pks: bytes, pk_len: int):
         """KeyValidate on the GPU: (96-byte uncompressed keys, status int8 array)."""

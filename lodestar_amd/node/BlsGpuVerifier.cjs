@@ -13,6 +13,12 @@
  *     are waiting, then submitted together; every job keeps its own result (index.ts:41-57, 238-285).
  *     Non-batchable jobs are submitted on the next macrotask, so a synchronous loop of calls coalesces
  *     into one submission (index.ts:276-283).
+ *   - verifySignatureSetsSameMessage(sets, message, opts) -> Promise<boolean[]> (interface.ts; multithread/index.ts
+ *     verifySignatureSetsSameMessage + jobItem.ts prepareWork / retry): the sets of the calls waiting in one flush are
+ *     aggregated with randomness in ONE device call (blst-ts aggregateWithRandomness, which the reference runs on the
+ *     main thread or a libuv worker), each call's (P, message, S) is verified as an ordinary job, and a call whose
+ *     aggregate is rejected or does not verify is retried set by set; a bad signature is a `false`, never a throw.
+ *   - canAcceptWork(): fewer than MAX_JOBS_CAN_ACCEPT_WORK jobs pending (index.ts:60, 199-205).
  *   - close() rejects buffered and queued jobs with QUEUE_ERROR_QUEUE_ABORTED (index.ts:176-197) and
  *     destroys the device context.
  *
@@ -49,6 +55,7 @@ const addon = require(path.join(__dirname, "blsgpu_napi.node"));
 
 const MAX_BUFFERED_SIGS = 32; // multithread/index.ts:48
 const MAX_BUFFER_WAIT_MS = 100; // multithread/index.ts:57
+const MAX_JOBS_CAN_ACCEPT_WORK = 512; // multithread/index.ts:60
 const QUEUE_ABORTED = "QUEUE_ERROR_QUEUE_ABORTED"; // util/queue/errors.ts QueueErrorCode.QUEUE_ABORTED
 const SIG_STRIDE = 192;
 
@@ -97,6 +104,14 @@ class BlsGpuVerifier {
     this.inflight = new Set();
     this.pkIndexOf = new WeakMap();
     this.stats = {submissions: 0, jobs: 0, sets: 0, groups: 0, batchRetries: 0, batchSigsSuccess: 0, uniqueMessages: 0};
+    // same-message calls (blsThreadPool.sameMessageRetryJobs / sameMessageRetrySets; device aggregation calls)
+    this.stats.sameMessageRetries = 0;
+    this.stats.sameMessageRetrySets = 0;
+    this.stats.sameMessageAggregations = 0;
+    this.sameQueued = []; // same-message calls waiting for the next flush
+    this.sameTimer = null;
+    this.samePending = 0; // same-message calls not yet settled
+    this.jobsOnDevice = 0; // jobs of submissions not yet completed
     this.queueLength = 0; // submissions on the device (blsThreadPool.queueLength)
     const m = this.metrics && this.metrics.blsThreadPool;
     if (m && m.queueLength && m.queueLength.addCollect) m.queueLength.addCollect(() => m.queueLength.set(this.queueLength));
@@ -217,6 +232,46 @@ class BlsGpuVerifier {
     return p;
   }
 
+  /**
+   * IBlsVerifier.verifySignatureSetsSameMessage (interface.ts; multithread/index.ts): every set signs `message`.
+   * Resolves to one boolean per set; a malformed or invalid signature is `false` there.  Rejects for no sets (as
+   * verifySignatureSets does), a call-level failure or a closed verifier.
+   * @param {Array<{publicKey: any, signature: Uint8Array}>} sets
+   * @param {Uint8Array} message
+   * @param {{batchable?: boolean}} opts
+   * @returns {Promise<boolean[]>}
+   */
+  async verifySignatureSetsSameMessage(sets, message, opts = {}) {
+    if (this.closed) throw new QueueError({code: QUEUE_ABORTED});
+    if (sets.length === 0) throw new Error(opts.verifyOnMainThread ? "Empty signature set" : "Empty results array");
+    const refs = sets.map((s) => this.pkRef(s.publicKey));
+    const table = refs.every((r) => r.index !== undefined);
+    if (!table)
+      for (const r of refs)
+        if (r.bytes === undefined || r.bytes.length !== 96)
+          throw new TypeError("BlsGpuVerifier: pubkeys of a bytes-mode job must serialize to 96 uncompressed bytes");
+    const call = {sets, refs, table, message, batchable: !!opts.batchable};
+    this.samePending++;
+    const p = new Promise((resolve, reject) => {
+      call.resolve = resolve;
+      call.reject = reject;
+    });
+    this.sameQueued.push(call);
+    if (!this.sameTimer) this.sameTimer = setTimeout(() => this.flushSameMessage(), 0);
+    this.inflight.add(p);
+    p.finally(() => {
+      this.samePending--;
+      this.inflight.delete(p);
+    }).catch(() => {});
+    return p;
+  }
+
+  /** IBlsVerifier.canAcceptWork: true while fewer than MAX_JOBS_CAN_ACCEPT_WORK jobs are pending. */
+  canAcceptWork() {
+    const buffered = this.bufferedJobs ? this.bufferedJobs.jobs.length : 0;
+    return buffered + this.queued.length + this.jobsOnDevice + this.samePending < MAX_JOBS_CAN_ACCEPT_WORK;
+  }
+
   /** IBlsVerifier.close (interface.ts:45). */
   async close() {
     if (this.closed) return;
@@ -231,12 +286,104 @@ class BlsGpuVerifier {
     this.queuedTimer = null;
     pending.push(...this.queued.splice(0, this.queued.length));
     for (const job of pending) job.reject(new QueueError({code: QUEUE_ABORTED}));
+    if (this.sameTimer) clearTimeout(this.sameTimer);
+    this.sameTimer = null;
+    for (const call of this.sameQueued.splice(0, this.sameQueued.length)) call.reject(new QueueError({code: QUEUE_ABORTED}));
     // in-flight submissions and aggregation calls complete (the device finishes them) before the context is freed
     await Promise.allSettled(Array.from(this.inflight));
     addon.close(this.ctx);
   }
 
   // ------------------------------------------------------------------------------------ internals
+  /** One device aggregation call per pubkey mode over the same-message calls that are waiting, one group per call. */
+  flushSameMessage() {
+    this.sameTimer = null;
+    const calls = this.sameQueued.splice(0, this.sameQueued.length);
+    for (const mode of [true, false]) {
+      const part = calls.filter((c) => c.table === mode);
+      if (part.length) this.aggregateSameMessage(part, mode);
+    }
+  }
+
+  aggregateSameMessage(calls, tableMode) {
+    let n = 0;
+    for (const c of calls) n += c.sets.length;
+    const groupFirst = new Uint32Array(calls.length + 1);
+    const sigs = new Uint8Array(SIG_STRIDE * n);
+    const sigLen = new Uint32Array(n);
+    const pkIndex = tableMode ? new Uint32Array(n) : null;
+    const pkBytes = tableMode ? null : new Uint8Array(96 * n);
+    let k = 0;
+    calls.forEach((c, ci) => {
+      groupFirst[ci] = k;
+      c.sets.forEach((s, i) => {
+        sigLen[k] = s.signature.length; // 96 / 192, anything else -> BLST_INVALID_SIZE: the call is retried per set
+        sigs.set(s.signature.subarray(0, Math.min(s.signature.length, SIG_STRIDE)), SIG_STRIDE * k);
+        if (tableMode) pkIndex[k] = c.refs[i].index;
+        else pkBytes.set(c.refs[i].bytes, 96 * k);
+        k++;
+      });
+    });
+    groupFirst[calls.length] = k;
+    this.stats.sameMessageAggregations++;
+    addon.aggregateWithRandomness(this.ctx, groupFirst, pkBytes, pkIndex, sigs, sigLen, SIG_STRIDE, this.seed, 96, SIG_STRIDE).then(
+      (r) => {
+        calls.forEach((c, ci) => {
+          const done =
+            r.status[ci] === 0
+              ? this.verifySameMessageAggregate(c, r.outPk.slice(96 * ci, 96 * ci + 96), r.outSig.slice(SIG_STRIDE * ci, SIG_STRIDE * (ci + 1)))
+              : this.retrySameMessage(c);
+          done.then(c.resolve, c.reject);
+        });
+      },
+      (err) => {
+        // call-level failure (device error, entropy, closed context): reject every call, never resolve false
+        for (const c of calls) c.reject(err.code === QUEUE_ABORTED ? new QueueError({code: QUEUE_ABORTED}) : err);
+      }
+    );
+  }
+
+  /** (P, message, S) as its own ordinary job; anything but `true` retries the call's sets one by one. */
+  async verifySameMessageAggregate(call, pk96, sig192) {
+    let ok = false;
+    try {
+      ok = await this.verifySignatureSets(
+        [{type: SignatureSetType.single, pubkey: pk96, signingRoot: call.message, signature: sig192}],
+        {batchable: call.batchable}
+      );
+    } catch (e) {
+      if (e instanceof QueueError || e.code) throw e; // call-level failure; a job error (BLST_ERROR) retries
+    }
+    if (ok) return call.sets.map(() => true);
+    return this.retrySameMessage(call);
+  }
+
+  /** Every set of the call as a one-set job, all in one submission: entry i is true iff its job's result is 1. */
+  retrySameMessage(call) {
+    if (this.closed) return Promise.reject(new QueueError({code: QUEUE_ABORTED}));
+    this.stats.sameMessageRetries++;
+    this.stats.sameMessageRetrySets += call.sets.length;
+    const m = this.metrics && this.metrics.blsThreadPool;
+    if (m && m.sameMessageRetryJobs) m.sameMessageRetryJobs.inc(1);
+    if (m && m.sameMessageRetrySets) m.sameMessageRetrySets.inc(call.sets.length);
+    const jobs = [];
+    const results = call.sets.map(
+      (s) =>
+        new Promise((resolve, reject) => {
+          const job = this.encodeJob(
+            [{type: SignatureSetType.single, pubkey: s.publicKey, signingRoot: call.message, signature: s.signature}],
+            {batchable: call.batchable}
+          );
+          job.addedTimeMs = Date.now();
+          job.resolve = resolve;
+          job.reject = reject;
+          jobs.push(job);
+        })
+    );
+    this.dispatch(jobs);
+    return Promise.all(results).then((codes) => codes.map((c) => c === 1));
+  }
+
   flushBuffered() {
     const b = this.bufferedJobs;
     this.bufferedJobs = null;
@@ -335,9 +482,11 @@ class BlsGpuVerifier {
     }
     const submitNs = process.hrtime.bigint();
     this.queueLength += 1;
+    this.jobsOnDevice += jobs.length;
     const p = addon.submit(this.ctx, req).then(
       (out) => {
         this.queueLength -= 1;
+        this.jobsOnDevice -= jobs.length;
         const st = this.stats;
         st.submissions++;
         st.jobs += jobs.length;
@@ -369,6 +518,7 @@ class BlsGpuVerifier {
       },
       (err) => {
         this.queueLength -= 1;
+        this.jobsOnDevice -= jobs.length;
         // call-level failure (device error, closed context): reject every job, never resolve false
         for (const j of jobs) j.reject(err.code === QUEUE_ABORTED ? new QueueError({code: QUEUE_ABORTED}) : err);
       }
@@ -459,6 +609,7 @@ module.exports = {
   SignatureSetType,
   MAX_BUFFERED_SIGS,
   MAX_BUFFER_WAIT_MS,
+  MAX_JOBS_CAN_ACCEPT_WORK,
   JOB_BATCHABLE,
   JOB_URGENT,
   addon,

@@ -28,6 +28,11 @@
  *     blsgpu_aggregate_signatures as napi_create_async_work: the inputs are copied before it returns, the C call
  *     runs on a libuv worker thread and the promise settles on the main thread (the event loop is never blocked).
  *     close(ctx) throws while such calls are outstanding: the JS class waits for them first.
+ *   aggregateWithRandomness(ctx, groupFirst: Uint32Array, pkBytes: Uint8Array | null, pkIndex: Uint32Array | null,
+ *                           sigs: Uint8Array, sigLen: Uint32Array, sigStride, seed, outPkLen 48|96, outSigLen 96|192)
+ *       -> Promise<{outPk: Uint8Array, outSig: Uint8Array, status: Int8Array, firstBad: Uint32Array}>
+ *     blsgpu_aggregate_with_randomness as napi_create_async_work, the same lifetime rules as aggregateSignatures
+ *     (seed 0 = fresh scalars; a non-zero seed, an integer below 2^53, only for comparison runs).
  *   debugInject(what, skip, count)                                blsgpu_debug_inject (only with BLSGPU_FAULT_INJECTION=1)
  */
 #define NAPI_VERSION 6
@@ -49,7 +54,7 @@
 
 typedef struct {
   blsgpu_ctx* ctx;
-  uint32_t agg_pending; /* aggregateSignatures calls queued or running (main thread only) */
+  uint32_t agg_pending; /* aggregateSignatures / aggregateWithRandomness calls queued or running (main thread only) */
 } CtxBox;
 
 typedef struct {
@@ -134,7 +139,7 @@ static napi_value Close(napi_env env, napi_callback_info info) {
   if (!box) return NULL;
   if (box->ctx && box->agg_pending) {
     /* a queued worker still holds the context: destroying it now would free it under that call */
-    napi_throw_error(env, "BLSGPU_ERR_ARGS", "close: aggregateSignatures calls are outstanding");
+    napi_throw_error(env, "BLSGPU_ERR_ARGS", "close: aggregation calls are outstanding");
     return NULL;
   }
   if (box->ctx) {
@@ -568,6 +573,164 @@ static napi_value AggregateSignatures(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* aggregateWithRandomness: one blsgpu_aggregate_with_randomness call as async work */
+typedef struct {
+  CtxBox* box;
+  uint32_t n_groups, stride, out_pk_len, out_sig_len;
+  uint64_t seed;
+  uint32_t* group_first;
+  uint8_t* pk_bytes;
+  uint32_t* pk_index;
+  uint32_t* sig_len;
+  uint8_t* sigs;
+  uint8_t* out_pk;
+  uint8_t* out_sig;
+  int8_t* status;
+  uint32_t* first_bad;
+  int rc;
+  napi_deferred deferred;
+  napi_async_work work;
+} AwrCall;
+
+static void awr_free(AwrCall* a) {
+  free(a->group_first);
+  free(a->pk_bytes);
+  free(a->pk_index);
+  free(a->sig_len);
+  free(a->sigs);
+  free(a->out_pk);
+  free(a->out_sig);
+  free(a->status);
+  free(a->first_bad);
+  free(a);
+}
+
+/* libuv worker thread */
+static void awr_execute(napi_env env, void* data) {
+  (void)env;
+  AwrCall* a = (AwrCall*)data;
+  a->rc = blsgpu_aggregate_with_randomness(a->box->ctx, a->n_groups, a->group_first, a->pk_bytes, a->pk_index, a->sigs,
+                                           a->stride, a->sig_len, a->seed, a->out_pk, a->out_pk_len, a->out_sig,
+                                           a->out_sig_len, a->status, a->first_bad);
+}
+
+/* JS main thread */
+static void awr_complete(napi_env env, napi_status st, void* data) {
+  AwrCall* a = (AwrCall*)data;
+  a->box->agg_pending--;
+  if (st != napi_ok || a->rc != BLSGPU_OK) {
+    const char* name = blsgpu_code_name(st != napi_ok ? BLSGPU_ERR_CLOSED : a->rc);
+    napi_value msg, code, err;
+    napi_create_string_utf8(env, name ? name : "BLSGPU_DEVICE_ERROR", NAPI_AUTO_LENGTH, &msg);
+    napi_create_string_utf8(env, name ? name : "BLSGPU_DEVICE_ERROR", NAPI_AUTO_LENGTH, &code);
+    napi_create_error(env, code, msg, &err);
+    napi_reject_deferred(env, a->deferred, err);
+  } else {
+    napi_value out;
+    napi_create_object(env, &out);
+    napi_set_named_property(env, out, "outPk",
+                            copy_out(env, napi_uint8_array, a->out_pk, (size_t)a->n_groups * a->out_pk_len, 1));
+    napi_set_named_property(env, out, "outSig",
+                            copy_out(env, napi_uint8_array, a->out_sig, (size_t)a->n_groups * a->out_sig_len, 1));
+    napi_set_named_property(env, out, "status", copy_out(env, napi_int8_array, a->status, a->n_groups, 1));
+    napi_set_named_property(env, out, "firstBad", copy_out(env, napi_uint32_array, a->first_bad, a->n_groups, 4));
+    napi_resolve_deferred(env, a->deferred, out);
+  }
+  napi_delete_async_work(env, a->work);
+  awr_free(a);
+}
+
+/* a typed array of the wanted type, or null / undefined (*data stays NULL); -1 = anything else */
+static int opt_typed(napi_env env, napi_value v, napi_typedarray_type want, void** data, size_t* len) {
+  napi_valuetype vt;
+  *data = NULL;
+  *len = 0;
+  if (napi_typeof(env, v, &vt) != napi_ok) return -1;
+  if (vt == napi_null || vt == napi_undefined) return 0;
+  napi_typedarray_type t;
+  if (napi_get_typedarray_info(env, v, &t, len, data, NULL, NULL) != napi_ok || t != want) return -1;
+  if (!*data) *data = (void*)""; /* an empty array is still "given" */
+  return 0;
+}
+
+static napi_value AggregateWithRandomness(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value argv[10];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 10) {
+    napi_throw_type_error(env, NULL,
+                          "aggregateWithRandomness(ctx, groupFirst, pkBytes, pkIndex, sigs, sigLen, sigStride, seed, "
+                          "outPkLen, outSigLen)");
+    return NULL;
+  }
+  CtxBox* box = get_open_box(env, argv[0]);
+  if (!box) return NULL;
+  size_t n_gf = 0, n_pkb = 0, n_pki = 0, n_bytes = 0, n_len = 0;
+  void *gf = NULL, *pkb = NULL, *pki = NULL, *sigs = NULL, *slen = NULL;
+  if (opt_typed(env, argv[1], napi_uint32_array, &gf, &n_gf) || !gf ||
+      opt_typed(env, argv[2], napi_uint8_array, &pkb, &n_pkb) ||
+      opt_typed(env, argv[3], napi_uint32_array, &pki, &n_pki) ||
+      opt_typed(env, argv[4], napi_uint8_array, &sigs, &n_bytes) || !sigs ||
+      opt_typed(env, argv[5], napi_uint32_array, &slen, &n_len) || !slen) {
+    napi_throw_type_error(env, NULL,
+                          "aggregateWithRandomness: groupFirst, pkIndex, sigLen Uint32Array; pkBytes, sigs Uint8Array");
+    return NULL;
+  }
+  uint32_t stride = 0, out_pk_len = 0, out_sig_len = 0;
+  double seed = 0;
+  napi_get_value_uint32(env, argv[6], &stride);
+  napi_get_value_double(env, argv[7], &seed);
+  napi_get_value_uint32(env, argv[8], &out_pk_len);
+  napi_get_value_uint32(env, argv[9], &out_sig_len);
+  /* shape checks on the host before anything is queued */
+  const uint32_t* gfw = (const uint32_t*)gf;
+  int ok = n_gf >= 1 && stride >= 96 && (out_pk_len == 48 || out_pk_len == 96) &&
+           (out_sig_len == 96 || out_sig_len == 192) && gfw[0] == 0 && (pkb != NULL) != (pki != NULL) && seed >= 0 &&
+           seed < 9007199254740992.0;
+  for (size_t g = 0; ok && g + 1 < n_gf; g++) ok = gfw[g + 1] >= gfw[g];
+  ok = ok && gfw[n_gf - 1] == n_len && n_len <= (1u << 20) && n_bytes >= (size_t)stride * n_len;
+  ok = ok && (pkb ? n_pkb == 96 * n_len : n_pki == n_len);
+  for (size_t k = 0; ok && stride < 192 && k < n_len; k++) ok = ((const uint32_t*)slen)[k] != 192;
+  if (!ok) {
+    napi_throw_range_error(env, "BLSGPU_ERR_ARGS", "aggregateWithRandomness: inconsistent array sizes");
+    return NULL;
+  }
+  AwrCall* a = (AwrCall*)calloc(1, sizeof(AwrCall));
+  a->box = box;
+  a->n_groups = (uint32_t)n_gf - 1;
+  a->stride = stride;
+  a->out_pk_len = out_pk_len;
+  a->out_sig_len = out_sig_len;
+  a->seed = (uint64_t)seed;
+  a->group_first = (uint32_t*)dup_bytes(gf, n_gf * 4);
+  if (pkb) a->pk_bytes = (uint8_t*)dup_bytes(pkb, n_pkb);
+  if (pki) a->pk_index = (uint32_t*)dup_bytes(pki, n_pki * 4);
+  a->sig_len = (uint32_t*)dup_bytes(slen, n_len * 4);
+  a->sigs = (uint8_t*)dup_bytes(sigs, (size_t)stride * n_len);
+  a->out_pk = (uint8_t*)calloc((size_t)a->n_groups * out_pk_len + 1, 1);
+  a->out_sig = (uint8_t*)calloc((size_t)a->n_groups * out_sig_len + 1, 1);
+  a->status = (int8_t*)calloc((size_t)a->n_groups + 1, 1);
+  a->first_bad = (uint32_t*)calloc((size_t)a->n_groups + 1, 4);
+  napi_value promise, name;
+  if (!a->group_first || (!a->pk_bytes && !a->pk_index) || !a->sig_len || !a->sigs || !a->out_pk || !a->out_sig ||
+      !a->status || !a->first_bad || napi_create_promise(env, &a->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "blsgpu_aggregate_with_randomness", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, NULL, name, awr_execute, awr_complete, a, &a->work) != napi_ok) {
+    awr_free(a);
+    napi_throw_error(env, NULL, "aggregateWithRandomness: could not queue the call");
+    return NULL;
+  }
+  box->agg_pending++;
+  if (napi_queue_async_work(env, a->work) != napi_ok) {
+    box->agg_pending--;
+    napi_delete_async_work(env, a->work);
+    awr_free(a);
+    napi_throw_error(env, NULL, "aggregateWithRandomness: could not queue the call");
+    return NULL;
+  }
+  return promise;
+}
+
 /* debugInject(what, skip, count): blsgpu_debug_inject (test hook; BLSGPU_INJECT_ENTROPY 1, BLSGPU_INJECT_DEVICE 2) */
 static napi_value DebugInject(napi_env env, napi_callback_info info) {
   size_t argc = 3;
@@ -600,6 +763,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
       {"submit", NULL, Submit, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"keyValidate", NULL, KeyValidate, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"aggregateSignatures", NULL, AggregateSignatures, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
+      {"aggregateWithRandomness", NULL, AggregateWithRandomness, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   /* the fault-injection test hook is exported, by its own definition, only to processes started with

@@ -35,6 +35,32 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
   /** IBlsVerifier.verifySignatureSets: true iff every set verifies; rejects with "BLST_ERROR: <CODE>" where the
    * reference's Signature.fromBytes throws, "QUEUE_ERROR_QUEUE_ABORTED" once closed. */
   verifySignatureSets(sets: ISignatureSet[], opts?: VerifySignatureOpts): Promise<boolean>;
+  /** IBlsVerifier.verifySignatureSetsSameMessage: one boolean per set, all signing `message`.  The calls waiting in
+   * one flush share one device aggregateWithRandomness call; each call's (P, message, S) is verified as an ordinary
+   * job, and a call whose aggregate is rejected or does not verify is retried set by set (stats.sameMessageRetries).
+   * A malformed or invalid signature is `false`; rejects for no sets, a call-level failure or once closed. */
+  verifySignatureSetsSameMessage(
+    sets: {publicKey: GpuPubkey; signature: Uint8Array}[],
+    message: Uint8Array,
+    opts?: Omit<VerifySignatureOpts, "verifyOnMainThread">
+  ): Promise<boolean[]>;
+  /** IBlsVerifier.canAcceptWork: true while fewer than MAX_JOBS_CAN_ACCEPT_WORK (512) jobs are pending. */
+  canAcceptWork(): boolean;
+  readonly stats: {
+    submissions: number;
+    jobs: number;
+    sets: number;
+    groups: number;
+    batchRetries: number;
+    batchSigsSuccess: number;
+    uniqueMessages: number;
+    /** same-message calls retried set by set, and their sets (blsThreadPool.sameMessageRetryJobs / ...Sets) */
+    sameMessageRetries: number;
+    sameMessageRetrySets: number;
+    /** device aggregateWithRandomness calls */
+    sameMessageAggregations: number;
+    urgentCalls?: number;
+  };
   /** Signature.aggregate(group.map(fromBytes)).toBytes() for every group in one device call, off the main thread (the
    * op pools' fold, chain/opPools/*.ts).  One entry per group: the aggregate (96 bytes compressed, 192 with
    * compressed: false) or, for a rejected group, the Error the reference throws ("BLST_ERROR: <NAME>",
@@ -74,4 +100,5 @@ export declare function ethFastAggregateVerify(
 export declare const SignatureSetType: {single: "single"; aggregate: "aggregate"};
 export declare const MAX_BUFFERED_SIGS: number;
 export declare const MAX_BUFFER_WAIT_MS: number;
+export declare const MAX_JOBS_CAN_ACCEPT_WORK: number;
 export declare const addon: Record<string, (...args: unknown[]) => unknown>;
