@@ -25,6 +25,9 @@
  *                                      multithread/index.ts, jobItem.ts `SameMessage`; gossip attestations sharing one
  *                                      AttestationData, chain/validation/attestation.ts
  *                                      validateGossipAttestationsSameAttData)
+ *   blsgpu_verify_same_message      <- the whole of IBlsVerifier.verifySignatureSetsSameMessage: the `SameMessage` job's
+ *                                      aggregateWithRandomness + verify of the aggregate, and the worker's retry of a
+ *                                      failed job set by set (multithread/index.ts, jobItem.ts, worker.ts)
  *   blsgpu_key_validate             <- PublicKey.fromBytes(pk, CoordType.affine, validate = true) for untrusted
  *                                      keys (state-transition/src/block/processDeposit.ts:56-64,
  *                                      beacon-node/test/spec/general/bls.ts:33-42)
@@ -51,7 +54,8 @@ extern "C" {
 #endif
 
 /* Bumped when an existing entry point or struct changes.  Entry points added since 8, which leave every existing one
- * as it was and so keep the number: blsgpu_randomness_words, blsgpu_aggregate_with_randomness, blsgpu_awr_lanes. */
+ * as it was and so keep the number: blsgpu_randomness_words, blsgpu_aggregate_with_randomness, blsgpu_awr_lanes,
+ * blsgpu_verify_same_message, blsgpu_same_message_form. */
 #define BLSGPU_ABI_VERSION 8
 
 /* blsgpu_batch.job_flags bits (reference VerifySignatureOpts, chain/bls/interface.ts:3-18) */
@@ -311,6 +315,45 @@ int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const u
 /* Lanes per group the segmented sum of such a call takes (64 = a wave per group with an LDS tree; 32, 16, 8 = lane
  * groups with a shuffle butterfly; 1 = a lane per group): non-increasing in n_groups.  Pure host code. */
 uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets);
+
+#define BLSGPU_SAME_LANE_FORMS 1u /* diagnostics / tests: take the large-call kernel forms whatever the size */
+
+typedef struct blsgpu_same_message_stats {
+  uint32_t groups_accepted; /* non-empty groups whose aggregate check held: every set 1 */
+  uint32_t groups_retried;  /* non-empty groups verified set by set */
+  uint32_t retry_sets;      /* their sets */
+  uint32_t unique_messages; /* distinct messages over all groups of the call */
+  uint32_t form;            /* bit 0: group phase took the lane forms, bit 1: retry phase did (0 = cooperative) */
+  double device_ms;         /* host clock around the device work of the call */
+} blsgpu_same_message_stats;
+
+/* verifySignatureSetsSameMessage for n_groups groups in one call: the randomized aggregation of
+ * blsgpu_aggregate_with_randomness, each group's pairing check and the per-set retry of the groups that fail, without
+ * leaving the device in between.  Groups, keys (trusted: bytes mode, or table mode), signatures (always
+ * subgroup-checked), seed and scalars are exactly as in blsgpu_aggregate_with_randomness; set k of group g signs
+ * msgs[32 g].
+ * A non-empty group that the aggregation accepts and whose FinalExp(MillerLoop(P_g, H(m_g)) * MillerLoop(-g1, S_g)) == 1
+ * gets set_result 1 for every set and group_result 1 (P_g equal to the identity counts as a failed check).  Every
+ * other non-empty group gets group_result 0 and each of its sets is verified on its own with r = 1: set_result[k] is
+ * what blsgpu_verify answers for that set as a one-set non-batchable job -- 1, 0 (an identity signature too) or -code,
+ * the key's error before the signature's.  An empty group has group_result -BLSGPU_EMPTY_AGGREGATE and no set.  Groups
+ * never affect each other.  A HIP failure returns BLSGPU_DEVICE_ERROR with nothing written: the call never writes a 0
+ * it did not compute.  seed 0 without OS entropy returns BLSGPU_ERR_ENTROPY with nothing written.
+ * Malformed arguments (a null pointer other than group_result / stats, both or neither of pk_bytes / pk_index,
+ * sig_stride < 96, an unknown flag, a group_first not non-decreasing from 0 or above 1 << 20 sets, a 192-byte signature
+ * in a narrower stride) return BLSGPU_ERR_ARGS before anything is read or reaches the device, as does a table index
+ * beyond the table; n_groups == 0 returns BLSGPU_OK.
+ * Runs on device 0 beside verification calls: the signature decode and sum on the helper stream, the key sum and the
+ * messages' hash_to_G2 on two helper streams of their own, joined before the checks. */
+int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
+                               const uint8_t* msgs /* [32 * n_groups] */, const uint8_t* pk_bytes,
+                               const uint32_t* pk_index, const uint8_t* sigs, uint32_t sig_stride,
+                               const uint32_t* sig_len, uint64_t seed, uint32_t flags,
+                               int8_t* set_result /* [n_sets] */, int8_t* group_result /* [n_groups], nullable */,
+                               blsgpu_same_message_stats* stats /* nullable */);
+/* 0 = cooperative forms, 1 = lane forms for a phase of n_items pairings: at most 512 items (the default of option
+ * "coop_max") are cooperative unless BLSGPU_SAME_LANE_FORMS is set.  Pure host code. */
+uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags);
 
 /* KeyValidate of n untrusted pubkeys (pks[stride * i], pk_len 48 compressed or 96 uncompressed): status[i]
  * = 0 or BAD_ENCODING / POINT_NOT_ON_CURVE / PK_IS_INFINITY / POINT_NOT_IN_GROUP; out96 (nullable)

@@ -204,3 +204,22 @@ def verify_signature_sets_same_message(ctx: Context, sets, message: bytes, seed=
     res, _ = ctx.verify_raw(np.arange(n + 1), buf, sig_len, message * n, job_flags=np.ones(n), sig_stride=stride,
                             **keys)
     return [int(r) == 1 for r in res]
+
+
+def verify_same_message_groups(ctx: Context, groups, messages, seed=0):
+    """verifySignatureSetsSameMessage for many groups in ONE device call (Context.verify_same_message): groups[g] =
+    [(pk96 or table index, signature bytes)] all signing messages[g]; a list with one list of bools per group, each
+    what verify_signature_sets_same_message answers for that group.  An empty group gives an empty list."""
+    groups = [list(g) for g in groups]
+    messages = [bytes(m)[:32].ljust(32, b"\0") for m in messages]
+    if len(messages) != len(groups):
+        raise ValueError("one message per group")
+    if not groups:
+        return []
+    first = np.cumsum([0] + [len(g) for g in groups])
+    pkb, pki, buf, sig_len, stride = _same_message_arrays([s for g in groups for s in g])
+    if first[-1] == 0:
+        pkb = b""  # no set at all: either key mode
+    res, _, _ = ctx.verify_same_message(first, b"".join(messages), buf, pk_bytes=pkb, pk_index=pki, sig_len=sig_len,
+                                        sig_stride=stride, seed=seed)
+    return [[int(r) == 1 for r in res[first[g]: first[g + 1]]] for g in range(len(groups))]

@@ -157,12 +157,11 @@ uint32_t awr_launch_lanes(uint32_t n_groups, uint32_t L) {
   return (uint32_t)(((uint64_t)n_groups * L + WAVE - 1) / WAVE) * WAVE;
 }
 
-void launch_awr_sums(const AwrBuffers& a, uint32_t L, hipStream_t s) {
+template <class F>
+static void launch_awr_sum(const AwrBuffers& a, uint32_t L, hipStream_t s) {
   if (!a.n_groups) return;
   const dim3 grid(a.tab_n / WAVE);
-#define AWR_SUM(l)                                                   \
-  hipLaunchKernelGGL((k_awr_sum<fp, l>), grid, dim3(WAVE), 0, s, a); \
-  hipLaunchKernelGGL((k_awr_sum<fp2, l>), grid, dim3(WAVE), 0, s, a)
+#define AWR_SUM(l) hipLaunchKernelGGL((k_awr_sum<F, l>), grid, dim3(WAVE), 0, s, a)
   switch (L) {
     case 64: AWR_SUM(64); break;
     case 32: AWR_SUM(32); break;
@@ -171,6 +170,12 @@ void launch_awr_sums(const AwrBuffers& a, uint32_t L, hipStream_t s) {
     default: AWR_SUM(1); break;
   }
 #undef AWR_SUM
+}
+void launch_awr_sum_pk(const AwrBuffers& a, uint32_t L, hipStream_t s) { launch_awr_sum<fp>(a, L, s); }
+void launch_awr_sum_sig(const AwrBuffers& a, uint32_t L, hipStream_t s) { launch_awr_sum<fp2>(a, L, s); }
+void launch_awr_sums(const AwrBuffers& a, uint32_t L, hipStream_t s) {
+  launch_awr_sum_pk(a, L, s);
+  launch_awr_sum_sig(a, L, s);
 }
 void launch_awr_serialize(const AwrBuffers& a, uint8_t* out_pk, uint32_t out_pk_len, uint8_t* out_sig,
                           uint32_t out_sig_len, int8_t* status, uint32_t* first_bad, hipStream_t s) {

@@ -256,6 +256,26 @@ inline uint32_t awr_lanes(uint32_t n_groups, uint32_t n_sets) {
 uint32_t awr_launch_lanes(uint32_t n_groups, uint32_t L);
 // sum_pk / sum_sig and the per-group first errors, on L lanes per group (a.tab_n = awr_launch_lanes(n_groups, L))
 void launch_awr_sums(const AwrBuffers& a, uint32_t L, hipStream_t s);
+// its two halves on their own: sum_pk and the keys' first errors / sum_sig and the signatures'.  They share nothing
+// but a.tab, so two copies of `a` with different window scratch may run on two streams at once.
+void launch_awr_sum_pk(const AwrBuffers& a, uint32_t L, hipStream_t s);
+void launch_awr_sum_sig(const AwrBuffers& a, uint32_t L, hipStream_t s);
+// One-call same-message verification (k_same.hip, blsgpu_verify_same_message).
+// per group: pk_aff (W_G1A, stride n_groups) = sum_pk times inv = 1 / z (launch_batch_inv), code = the group's AWR
+// status, include = accepted by AWR with a finite P
+void launch_same_group_items(const AwrBuffers& a, const uint32_t* inv, uint32_t* pk_aff, uint8_t* include, int8_t* code,
+                             hipStream_t s);
+// per retried set q = set list[q]: pk_aff (W_G1A) and S (W_G2J, the decoded signature with z = 1), stride n_retry;
+// code = its first error (key, then signature), include = no error and a finite signature
+void launch_same_retry_items(const AwrBuffers& a, const uint32_t* list, uint32_t n_retry, uint32_t* pk_aff, uint32_t* S,
+                             uint8_t* include, int8_t* code, hipStream_t s);
+// group_result[g] = 1 / 0 / -EMPTY_AGGREGATE and set_result[k] = 1 for every set of an accepted group, else 0
+void launch_same_group_results(const uint32_t* group_first, uint32_t n_groups, uint32_t n_sets, const uint8_t* include,
+                               const int8_t* code, const uint8_t* ok, int8_t* set_result, int8_t* group_result,
+                               hipStream_t s);
+// set_result[list[q]] = -code[q], or include[q] && ok[q]
+void launch_same_retry_results(const uint32_t* list, uint32_t n_retry, const uint8_t* include, const int8_t* code,
+                               const uint8_t* ok, int8_t* set_result, hipStream_t s);
 // both sums' toBytes(): out_pk[out_pk_len * g] (48 compressed / 96), out_sig[out_sig_len * g] (96 compressed / 192),
 // zeros for a rejected or empty group; status[g] / first_bad[g] = the group's status and its rejected set's index
 void launch_awr_serialize(const AwrBuffers& a, uint8_t* out_pk, uint32_t out_pk_len, uint8_t* out_sig,

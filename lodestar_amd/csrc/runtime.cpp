@@ -254,6 +254,10 @@ struct Device {
   std::mutex enq_mu;  // one run's batch (or fallback) launches are enqueued without another slot's in between
   std::mutex helper_mu;
   Slot helper;  // buffers of the synchronous helpers (on table_stream)
+  // blsgpu_verify_same_message (under helper_mu): the streams of its key-sum and message branches and the events that
+  // join them into table_stream, created by the first such call
+  hipStream_t same_st[2] = {};
+  hipEvent_t same_ev[3] = {};
   // pubkey table (AoS, W_PKTAB words per key): verification holds it shared, uploads exclusive
   std::shared_mutex table_mu;
   DevBuf<uint32_t> table;
@@ -2317,6 +2321,10 @@ void destroy_device(Device* d) {
     if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
   for (hipStream_t st : d->ust)
     if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
+  for (hipStream_t st : d->same_st)
+    if (st) (void)hipStreamSynchronize(st), (void)hipStreamDestroy(st);
+  for (hipEvent_t e : d->same_ev)
+    if (e) (void)hipEventDestroy(e);
   d->helper.release_all();
   d->table.release();
   if (d->table_stream) (void)hipStreamDestroy(d->table_stream);
@@ -3285,6 +3293,314 @@ int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const u
 }
 
 uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets) { return awr_lanes(n_groups, n_sets); }
+
+// ---- one-call same-message verification ------------------------------------------------------------------------
+// A phase of at most kSameCoopMax pairings takes the cooperative kernels (a workgroup per Miller loop and per check:
+// latency), a larger one the lane forms (throughput).  512 is option "coop_max"'s default, taken as a constant: the
+// helper calls read no option.
+constexpr uint32_t kSameCoopMax = 512;
+uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags) {
+  return (flags & BLSGPU_SAME_LANE_FORMS) || n_items > kSameCoopMax ? 1u : 0u;
+}
+namespace {
+// diagnostics (tools/bench_same_message.py): the three branches of the group phase on one stream
+inline bool same_serial() {
+  static const bool on = [] {
+    const char* v = getenv("BLSGPU_SAME_SERIAL");
+    return v && v[0] == '1';
+  }();
+  return on;
+}
+// Miller values and checks of one phase: item i < n_items pairs pk_aff[i] (W_G1A, stride n_items) with H(msg_idx[i]) when
+// include[i], and ok[i] = FinalExp(F_i * MillerLoop(-g1, S_i)) == 1 with S (W_G2J, stride n_items).  iota = 0, 1, ..,
+// n_items: one item per Miller chunk.  Cooperative form: k_miller_coop and k_group_check with its own Miller loop.
+// Lane form: the messages' stored lines (pm.lines), k_miller_acc6 (six lanes per pairing), MillerLoop(-g1, S) on one
+// lane per item and the final exponentiation on six (k_group_check6).
+void same_pairing_phase(const PipelineBuffers& pm, uint32_t n_items, const uint32_t* iota, uint32_t* pk_aff,
+                        uint8_t* include, const uint32_t* msg_idx, const uint32_t* S, uint32_t* F, uint32_t* Gs,
+                        uint8_t* ok, bool lane, hipStream_t s) {
+  PipelineBuffers pb = pm;
+  pb.n = n_items;
+  pb.pk_aff = pk_aff;
+  pb.include = include;
+  pb.msg_idx = msg_idx;
+  pb.n_chunks = n_items;
+  pb.chunk_first = iota;
+  pb.chunk_items = iota;
+  pb.f_chunk = F;
+  if (!lane) {
+    launch_miller_coop(pb, false, s, false);
+    launch_group_check(S, F, n_items, ok, s);
+  } else {
+    launch_miller_acc6(pb, false, s);
+    launch_group_sig_miller(S, n_items, Gs, s, false, true);
+    launch_group_check6(F, Gs, n_items, ok, s);
+  }
+}
+}  // namespace
+
+int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first, const uint8_t* msgs,
+                               const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
+                               uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed, uint32_t flags,
+                               int8_t* set_result, int8_t* group_result, blsgpu_same_message_stats* stats) {
+  if (!ctx || ctx->devs.empty() || !group_first || !msgs || !sigs || !sig_len || !set_result) return BLSGPU_ERR_ARGS;
+  if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
+  if (sig_stride < 96 || (flags & ~BLSGPU_SAME_LANE_FORMS)) return BLSGPU_ERR_ARGS;
+  if (n_groups == 0) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    return BLSGPU_OK;
+  }
+  if (group_first[0] != 0) return BLSGPU_ERR_ARGS;
+  for (uint32_t g = 0; g < n_groups; g++)
+    if (group_first[g + 1] < group_first[g]) return BLSGPU_ERR_ARGS;
+  const uint32_t n = group_first[n_groups], G = n_groups;
+  if (n > (1u << 20)) return BLSGPU_ERR_ARGS;
+  if (sig_stride < 192)
+    for (uint32_t k = 0; k < n; k++)
+      if (sig_len[k] == 192) return BLSGPU_ERR_ARGS;
+  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
+  // the call's scalars, before anything is written or reaches the device
+  std::vector<uint64_t> words(n);
+  uint64_t hash_key = 0;
+  {
+    batch_rand::Key key;
+    if (!resolve_key(seed, key, hash_key)) {
+      leave(ctx);
+      return BLSGPU_ERR_ENTROPY;
+    }
+    batch_rand::words(key, 0, n, words.data());
+  }
+  // messages, deduplicated as run_shard does: group g signs unique message gmsg[g]
+  std::vector<uint32_t> gmsg(G), uniq;
+  {
+    MsgIndex mi(G, hash_key ^ 0x6a09e667f3bcc908ull);
+    for (uint32_t g = 0; g < G; g++) gmsg[g] = mi.find_or_add(msgs, g, uniq);
+  }
+  const uint32_t U = (uint32_t)uniq.size();
+  Device* d = ctx->devs[0];
+  int rc = BLSGPU_OK;
+  std::vector<int8_t> h_set(n), h_grp(G);
+  blsgpu_same_message_stats st;
+  memset(&st, 0, sizeof st);
+  st.unique_messages = U;
+  bool streams_used = false;
+  try {
+    std::lock_guard<std::mutex> hl(d->helper_mu);
+    std::shared_lock<std::shared_mutex> tl(d->table_mu);
+    HIPCHK(hipSetDevice(d->id));
+    if (pk_index)
+      for (uint32_t k = 0; k < n; k++)
+        if (pk_index[k] >= d->table_n) rc = BLSGPU_ERR_ARGS;
+    if (rc == BLSGPU_OK) {
+      if (!d->same_st[0]) {
+        for (auto& e : d->same_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIPCHK(hipStreamCreateWithFlags(&d->same_st[1], hipStreamNonBlocking));
+        HIPCHK(hipStreamCreateWithFlags(&d->same_st[0], hipStreamNonBlocking));
+      }
+      const auto t0 = std::chrono::steady_clock::now();
+      const bool serial = same_serial();
+      hipStream_t s = d->table_stream, sb = serial ? s : d->same_st[0], sc = serial ? s : d->same_st[1];
+      const bool lane_g = blsgpu_same_message_form(G, flags) != 0;
+      const uint32_t L = awr_lanes(G, n), lanes = awr_launch_lanes(G, L);
+      // input arena: words | group_first | sig_len | sigs | keys | unique messages | group message indices | iota
+      const size_t key_bytes = pk_bytes ? (size_t)n * 96 : (size_t)n * 4;
+      const size_t o_gf = al256((size_t)n * 8), o_len = al256(o_gf + (size_t)(G + 1) * 4),
+                   o_sigs = al256(o_len + (size_t)n * 4), o_keys = al256(o_sigs + (size_t)n * sig_stride),
+                   o_umsg = al256(o_keys + key_bytes), o_gmsg = al256(o_umsg + (size_t)U * 32),
+                   o_iota = al256(o_gmsg + (size_t)G * 4), in_total = al256(o_iota + (size_t)(G + 1) * 4);
+      // byte arrays: error indices | error codes | signature status | signature flags | message flags | group include |
+      // group code | group verdict | group_result | set_result
+      const size_t b_ek = 0, b_ec = al256(b_ek + (size_t)G * 8), b_st = al256(b_ec + 2 * (size_t)G),
+                   b_fl = al256(b_st + n), b_mf = al256(b_fl + n), b_inc = al256(b_mf + U), b_code = al256(b_inc + G),
+                   b_ok = al256(b_code + G), b_gres = al256(b_ok + G), b_sres = al256(b_gres + G),
+                   bytes_total = al256(b_sres + n);
+      Slot& sl = d->helper;
+      // every buffer of the group phase grows here, while none of the three streams has work (each call ends with all
+      // of them synchronized); the retry phase grows only buffers the group phase does not use, after its synchronize
+      sl.d_in.ensure(in_total);
+      sl.d_bytes.ensure(bytes_total);
+      // work: sig_aff | window scratch of the G2 sum | of the G1 sum | sum_pk | sum_sig | pk_aff | 1 / z | F | G |
+      // message branch (inv, h_aff, h_jac, h_norm, h_prep, h_q)
+      const size_t nm = U;
+      sl.d_work.ensure((size_t)n * W_G2A + 2 * (size_t)lanes * AWR_TAB_WORDS +
+                       (size_t)G * (W_G1J + W_G2J + W_G1A + W_FP + 2 * W_FP12) +
+                       nm * (W_FP + W_G2A + W_G2J + W_FP + 14 * W_FP + 2 * W_G2J));
+      if (lane_g) sl.d_lines.ensure(nm * kMillerLineWords);
+      streams_used = true;
+      uint8_t* din = sl.d_in.p;
+      uint8_t* db = sl.d_bytes.p;
+      std::vector<uint32_t> iota((size_t)G + 1);
+      for (uint32_t g = 0; g <= G; g++) iota[g] = g;
+      std::vector<uint8_t> umsgs((size_t)U * 32);
+      for (uint32_t u = 0; u < U; u++) memcpy(umsgs.data() + (size_t)u * 32, msgs + (size_t)uniq[u] * 32, 32);
+      HIPCHK(hipMemcpyAsync(din + o_gf, group_first, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(din + o_umsg, umsgs.data(), (size_t)U * 32, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(din + o_gmsg, gmsg.data(), (size_t)G * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(din + o_iota, iota.data(), (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
+      if (n) {
+        HIPCHK(hipMemcpyAsync(din, words.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(din + o_len, sig_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(din + o_sigs, sigs, (size_t)n * sig_stride, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(din + o_keys, pk_bytes ? (const void*)pk_bytes : (const void*)pk_index, key_bytes,
+                              hipMemcpyHostToDevice, s));
+      }
+      PipelineBuffers pb;  // the signature decode
+      memset(&pb, 0, sizeof pb);
+      pb.n = n;
+      pb.sigs = din + o_sigs;
+      pb.sig_len = reinterpret_cast<uint32_t*>(din + o_len);
+      pb.sig_stride = sig_stride;
+      pb.flags = db + b_fl;
+      pb.status = reinterpret_cast<int8_t*>(db + b_st);
+      uint32_t* w = sl.d_work.p;
+      pb.sig_aff = w; w += (size_t)n * W_G2A;
+      AwrBuffers ab;
+      memset(&ab, 0, sizeof ab);
+      ab.n = n;
+      ab.n_groups = G;
+      ab.group_first = reinterpret_cast<uint32_t*>(din + o_gf);
+      ab.words = reinterpret_cast<uint64_t*>(din);
+      ab.pk_bytes = pk_bytes ? din + o_keys : nullptr;
+      ab.pk_index = pk_bytes ? nullptr : reinterpret_cast<uint32_t*>(din + o_keys);
+      ab.pk_table = d->table.p;
+      ab.pk_table_n = d->table_n;
+      ab.sig_aff = pb.sig_aff;
+      ab.sig_flags = pb.flags;
+      ab.sig_status = pb.status;
+      ab.tab = w; w += (size_t)lanes * AWR_TAB_WORDS;
+      ab.tab_n = lanes;
+      AwrBuffers ab_pk = ab;  // the G1 sum runs beside the G2 sum: its own window scratch
+      ab_pk.tab = w; w += (size_t)lanes * AWR_TAB_WORDS;
+      ab.sum_pk = ab_pk.sum_pk = w; w += (size_t)G * W_G1J;
+      ab.sum_sig = ab_pk.sum_sig = w; w += (size_t)G * W_G2J;
+      ab.err_k = ab_pk.err_k = reinterpret_cast<uint32_t*>(db + b_ek);
+      ab.err_c = ab_pk.err_c = reinterpret_cast<int8_t*>(db + b_ec);
+      uint32_t* g_pk_aff = w; w += (size_t)G * W_G1A;
+      uint32_t* g_inv = w; w += (size_t)G * W_FP;
+      uint32_t* g_F = w; w += (size_t)G * W_FP12;
+      uint32_t* g_G = w; w += (size_t)G * W_FP12;
+      PipelineBuffers pm;  // the message branch
+      memset(&pm, 0, sizeof pm);
+      pm.umsgs = din + o_umsg;
+      pm.n_umsg = U;
+      pm.nm = (uint32_t)nm;
+      pm.inv_buf = w; w += nm * W_FP;
+      pm.h_aff = w; w += nm * W_G2A;
+      pm.h_jac = w; w += nm * W_G2J;
+      pm.h_norm = w; w += nm * W_FP;
+      pm.h_prep = w; w += nm * 14 * W_FP;
+      pm.h_q = w;
+      pm.mflags = db + b_mf;
+      pm.lines = sl.d_lines.p;
+      uint8_t* g_inc = db + b_inc;
+      int8_t* g_code = reinterpret_cast<int8_t*>(db + b_code);
+      uint8_t* g_ok = db + b_ok;
+      int8_t* d_gres = reinterpret_cast<int8_t*>(db + b_gres);
+      int8_t* d_sres = reinterpret_cast<int8_t*>(db + b_sres);
+      const uint32_t* d_gmsg = reinterpret_cast<uint32_t*>(din + o_gmsg);
+      const uint32_t* d_iota = reinterpret_cast<uint32_t*>(din + o_iota);
+      // ---- group phase: three branches from the input copy, joined into s
+      HIPCHK(hipEventRecord(d->same_ev[0], s));
+      if (!serial) {
+        HIPCHK(hipStreamWaitEvent(sb, d->same_ev[0], 0));
+        HIPCHK(hipStreamWaitEvent(sc, d->same_ev[0], 0));
+      }
+      // (a) signatures: decode + subgroup check (cooperative for small calls, as small verification runs), S_g
+      launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, true);
+      launch_awr_sum_sig(ab, L, s);
+      // (b) keys: P_g and the batch inverses of its z
+      launch_awr_sum_pk(ab_pk, L, sb);
+      launch_batch_inv(ab.sum_pk, G, 2 * W_FP, g_inv, G, sb);
+      HIPCHK(hipEventRecord(d->same_ev[1], sb));
+      // (c) messages: H(m) affine, and in the lane form its Miller lines
+      bool have_lines = false;
+      launch_hash_to_g2(pm, sc, U <= 4096, false);
+      launch_h_affine(pm, sc);
+      if (lane_g) {
+        launch_miller_lines2(pm, sc);
+        have_lines = true;
+      }
+      HIPCHK(hipEventRecord(d->same_ev[2], sc));
+      if (!serial) {
+        HIPCHK(hipStreamWaitEvent(s, d->same_ev[1], 0));
+        HIPCHK(hipStreamWaitEvent(s, d->same_ev[2], 0));
+      }
+      launch_same_group_items(ab, g_inv, g_pk_aff, g_inc, g_code, s);
+      same_pairing_phase(pm, G, d_iota, g_pk_aff, g_inc, d_gmsg, ab.sum_sig, g_F, g_G, g_ok, lane_g, s);
+      launch_same_group_results(ab.group_first, G, n, g_inc, g_code, g_ok, d_sres, d_gres, s);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(h_grp.data(), d_gres, G, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
+      if (lane_g) st.form |= 1;
+      // ---- retry phase: every set of a non-empty group whose check did not hold, on its own with r = 1
+      std::vector<uint32_t> rlist, rmsg, riota;  // (alive until the final synchronize: they are copied from)
+      for (uint32_t g = 0; g < G; g++) {
+        if (group_first[g + 1] == group_first[g]) continue;
+        if (h_grp[g] == 1) {
+          st.groups_accepted++;
+          continue;
+        }
+        st.groups_retried++;
+        for (uint32_t k = group_first[g]; k < group_first[g + 1]; k++) {
+          rlist.push_back(k);
+          rmsg.push_back(gmsg[g]);
+        }
+      }
+      const uint32_t nr = (uint32_t)rlist.size();
+      st.retry_sets = nr;
+      if (nr) {
+        const bool lane_r = blsgpu_same_message_form(nr, flags) != 0;
+        // list | message indices | iota ; bytes: include | code | verdict
+        const size_t r_msg = al256((size_t)nr * 4) / 4, r_iota = r_msg + al256((size_t)nr * 4) / 4,
+                     r_total = r_iota + nr + 1;
+        sl.d_list.ensure(r_total);
+        sl.d_ok.ensure(3 * al256(nr));
+        sl.d_fb.ensure((size_t)nr * W_G1A);
+        sl.d_S.ensure((size_t)nr * W_G2J);
+        sl.d_F.ensure((size_t)nr * W_FP12);
+        if (lane_r) sl.d_G.ensure((size_t)nr * W_FP12);
+        if (lane_r && !have_lines) {
+          sl.d_lines.ensure(nm * kMillerLineWords);
+          pm.lines = sl.d_lines.p;
+        }
+        riota.resize((size_t)nr + 1);
+        for (uint32_t q = 0; q <= nr; q++) riota[q] = q;
+        uint32_t* dl = sl.d_list.p;
+        HIPCHK(hipMemcpyAsync(dl, rlist.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dl + r_msg, rmsg.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dl + r_iota, riota.data(), (size_t)(nr + 1) * 4, hipMemcpyHostToDevice, s));
+        uint8_t* r_inc = sl.d_ok.p;
+        int8_t* r_code = reinterpret_cast<int8_t*>(sl.d_ok.p + al256(nr));
+        uint8_t* r_ok = sl.d_ok.p + 2 * al256(nr);
+        launch_same_retry_items(ab, dl, nr, sl.d_fb.p, sl.d_S.p, r_inc, r_code, s);
+        if (lane_r && !have_lines) launch_miller_lines2(pm, s);
+        same_pairing_phase(pm, nr, dl + r_iota, sl.d_fb.p, r_inc, dl + r_msg, sl.d_S.p, sl.d_F.p, sl.d_G.p, r_ok, lane_r,
+                           s);
+        launch_same_retry_results(dl, nr, r_inc, r_code, r_ok, d_sres, s);
+        HIPCHK(hipGetLastError());
+        if (lane_r) st.form |= 2;
+      }
+      if (n) HIPCHK(hipMemcpyAsync(h_set.data(), d_sres, n, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      st.device_ms = ms_since(t0);
+    }
+  } catch (HipError&) {
+    rc = BLSGPU_DEVICE_ERROR;
+    // no branch may outlive the call: the next helper call reuses, and may grow, the buffers they work on
+    if (streams_used) {
+      (void)hipStreamSynchronize(d->table_stream);
+      for (hipStream_t x : d->same_st)
+        if (x) (void)hipStreamSynchronize(x);
+    }
+  }
+  if (rc == BLSGPU_OK) {  // results reach the caller only when every one of them was computed
+    if (n) memcpy(set_result, h_set.data(), n);
+    if (group_result) memcpy(group_result, h_grp.data(), G);
+    if (stats) *stats = st;
+  }
+  leave(ctx);
+  return rc;
+}
 
 int blsgpu_key_validate(blsgpu_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_t pk_len, uint32_t stride,
                         uint8_t* out96, int8_t* status) {

@@ -57,7 +57,10 @@ EXPORTED_SYMBOLS = [
     "blsgpu_randomness_words",
     "blsgpu_aggregate_with_randomness",
     "blsgpu_awr_lanes",
+    "blsgpu_verify_same_message",
+    "blsgpu_same_message_form",
 ]
+SAME_LANE_FORMS = 1
 ROOT_OBJECT = 0
 ROOT_ATTESTATION_DATA = 1
 
@@ -96,6 +99,17 @@ class Stats(ctypes.Structure):
         ("fallback_miller", ctypes.c_uint32),
         ("urgent_lane", ctypes.c_uint32),
         ("host_ms", ctypes.c_double),
+    ]
+
+
+class SameMessageStats(ctypes.Structure):
+    _fields_ = [
+        ("groups_accepted", ctypes.c_uint32),
+        ("groups_retried", ctypes.c_uint32),
+        ("retry_sets", ctypes.c_uint32),
+        ("unique_messages", ctypes.c_uint32),
+        ("form", ctypes.c_uint32),
+        ("device_ms", ctypes.c_double),
     ]
 
 
@@ -173,6 +187,10 @@ def load():
     lib.blsgpu_aggregate_with_randomness.restype = ctypes.c_int
     lib.blsgpu_awr_lanes.argtypes = [u32, u32]
     lib.blsgpu_awr_lanes.restype = u32
+    lib.blsgpu_verify_same_message.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, vp, ctypes.c_uint64, u32, vp, vp, vp]
+    lib.blsgpu_verify_same_message.restype = ctypes.c_int
+    lib.blsgpu_same_message_form.argtypes = [u32, u32]
+    lib.blsgpu_same_message_form.restype = u32
     _lib = lib
     return lib
 
@@ -246,6 +264,12 @@ def awr_lanes(n_groups, n_sets):
     """Lanes per group blsgpu_aggregate_with_randomness gives a call of this shape (C-ABI blsgpu_awr_lanes, pure host
     code): 64, 32, 16, 8 or 1."""
     return int(load().blsgpu_awr_lanes(n_groups, n_sets))
+
+
+def same_message_form(n_items, flags=0):
+    """The kernel forms blsgpu_verify_same_message gives a phase of n_items pairings (C-ABI blsgpu_same_message_form,
+    pure host code): 0 = cooperative, 1 = lane forms."""
+    return int(load().blsgpu_same_message_form(n_items, flags))
 
 
 def randomness_words(n, seed):
@@ -538,6 +562,40 @@ class Context:
             raise RuntimeError(f"blsgpu_aggregate_with_randomness -> {code_name(rc)}")
         return ([opk[out_pk_len * i: out_pk_len * (i + 1)].tobytes() for i in range(n)],
                 [osig[out_sig_len * i: out_sig_len * (i + 1)].tobytes() for i in range(n)], st[:n], fb[:n])
+
+    def verify_same_message(self, group_first, msgs, sigs, pk_bytes=None, pk_index=None, sig_len=None,
+                            sig_stride=None, seed=0, flags=0):
+        """verifySignatureSetsSameMessage for many groups in one device call (blsgpu_verify_same_message): group g owns
+        sets [group_first[g], group_first[g + 1]) and signs msgs[32 g]; sets as in aggregate_with_randomness.  Returns
+        (set_result int8 array: 1 / 0 / -code per set, group_result int8 array: 1 accepted / 0 verified set by set /
+        -9 empty, SameMessageStats).  ValueError for a malformed layout, before the library is called; RuntimeError
+        for a call-level failure."""
+        gf, buf, sl, stride, pkb, pki = awr_layout(group_first, sigs, pk_bytes, pk_index, sig_len, sig_stride)
+        n_groups = len(gf) - 1
+        n = int(gf[-1])
+        m = _u8(msgs)
+        if len(m) != 32 * n_groups:
+            raise ValueError(f"{n_groups} groups need {32 * n_groups} message bytes, got {len(m)}")
+        if len(m) == 0:
+            m = np.zeros(1, np.uint8)
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        if len(sl) == 0:
+            sl = np.zeros(1, np.uint32)
+        if pkb is not None and len(pkb) == 0:
+            pkb = np.zeros(1, np.uint8)
+        if pki is not None and len(pki) == 0:
+            pki = np.zeros(1, np.uint32)
+        res = np.zeros(max(n, 1), np.int8)
+        gres = np.zeros(max(n_groups, 1), np.int8)
+        st = SameMessageStats()
+        rc = self._lib.blsgpu_verify_same_message(
+            self.h, n_groups, gf.ctypes.data, m.ctypes.data, None if pkb is None else pkb.ctypes.data,
+            None if pki is None else pki.ctypes.data, buf.ctypes.data, stride, sl.ctypes.data, seed, flags,
+            res.ctypes.data, gres.ctypes.data, ctypes.byref(st))
+        if rc != OK:
+            raise RuntimeError(f"blsgpu_verify_same_message -> {code_name(rc)}")
+        return res[:n], gres[:n_groups], st
 
     def key_validate(self, pks: bytes, pk_len: int):
         """KeyValidate on the GPU: (96-byte uncompressed keys, status int8 array)."""

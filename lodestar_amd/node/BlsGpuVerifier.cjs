@@ -18,6 +18,8 @@
  *     aggregated with randomness in ONE device call (blst-ts aggregateWithRandomness, which the reference runs on the
  *     main thread or a libuv worker), each call's (P, message, S) is verified as an ordinary job, and a call whose
  *     aggregate is rejected or does not verify is retried set by set; a bad signature is a `false`, never a throw.
+ *     With the constructor option fusedSameMessage (default false) the flush is ONE addon.verifySameMessage call per
+ *     pubkey mode instead: aggregation, the aggregates' checks and the per-set retry all on the device.
  *   - canAcceptWork(): fewer than MAX_JOBS_CAN_ACCEPT_WORK jobs pending (index.ts:60, 199-205).
  *   - close() rejects buffered and queued jobs with QUEUE_ERROR_QUEUE_ABORTED (index.ts:176-197) and
  *     destroys the device context.
@@ -62,6 +64,7 @@ const SIG_STRIDE = 192;
 // job flags (include/blsgpu.h BLSGPU_JOB_*)
 const JOB_BATCHABLE = 1;
 const JOB_URGENT = 2;
+const SAME_LANE_FORMS = 1; // BLSGPU_SAME_LANE_FORMS
 
 // job codes (include/blsgpu.h enum blsgpu_code)
 const CODE_EMPTY_AGGREGATE = 9;
@@ -84,7 +87,10 @@ function jobError(code) {
 
 class BlsGpuVerifier {
   /**
-   * @param {{devices?: number[], groupSets?: number, groupPolicy?: number, seed?: number}} opts
+   * @param {{devices?: number[], groupSets?: number, groupPolicy?: number, seed?: number,
+   *          fusedSameMessage?: boolean}} opts  fusedSameMessage (default false): a flush of same-message calls is ONE
+   *          addon.verifySameMessage call per pubkey mode (aggregation, the aggregates' checks and the per-set retry on
+   *          the device) instead of an aggregation call followed by verification jobs
    * @param {{metrics?: object, logger?: object}} modules
    */
   constructor(opts = {}, modules = {}) {
@@ -93,6 +99,7 @@ class BlsGpuVerifier {
     // 1 = the pool's job / request / chunk structure (batchRetries / batchSigsSuccess in the reference's units)
     if (opts.groupPolicy) addon.setOption(this.ctx, "group_policy", opts.groupPolicy);
     this.seed = opts.seed || 0; // 0 = OS CSPRNG batch scalars; fixed only for comparison runs
+    this.fusedSameMessage = !!opts.fusedSameMessage;
     // verifyOnMainThread calls are latency-critical exceptions to the pool (the block proposer signature): they run on
     // the device's urgent lane.  The single-thread verifier sends every call that way and keeps the shared pipeline.
     this.urgentMainThread = true;
@@ -326,6 +333,7 @@ class BlsGpuVerifier {
     });
     groupFirst[calls.length] = k;
     this.stats.sameMessageAggregations++;
+    if (this.fusedSameMessage) return this.verifySameMessageFused(calls, groupFirst, pkBytes, pkIndex, sigs, sigLen);
     addon.aggregateWithRandomness(this.ctx, groupFirst, pkBytes, pkIndex, sigs, sigLen, SIG_STRIDE, this.seed, 96, SIG_STRIDE).then(
       (r) => {
         calls.forEach((c, ci) => {
@@ -334,6 +342,33 @@ class BlsGpuVerifier {
               ? this.verifySameMessageAggregate(c, r.outPk.slice(96 * ci, 96 * ci + 96), r.outSig.slice(SIG_STRIDE * ci, SIG_STRIDE * (ci + 1)))
               : this.retrySameMessage(c);
           done.then(c.resolve, c.reject);
+        });
+      },
+      (err) => {
+        // call-level failure (device error, entropy, closed context): reject every call, never resolve false
+        for (const c of calls) c.reject(err.code === QUEUE_ABORTED ? new QueueError({code: QUEUE_ABORTED}) : err);
+      }
+    );
+  }
+
+  /**
+   * fusedSameMessage: the whole method in one device call.  Call i resolves to one boolean per set (true iff its
+   * result is 1: a rejected set is false, as in the per-set retry); a group verified set by set counts as one retry.
+   */
+  verifySameMessageFused(calls, groupFirst, pkBytes, pkIndex, sigs, sigLen) {
+    const msgs = new Uint8Array(32 * calls.length);
+    calls.forEach((c, ci) => msgs.set(c.message.subarray(0, 32), 32 * ci));
+    addon.verifySameMessage(this.ctx, groupFirst, msgs, pkBytes, pkIndex, sigs, sigLen, SIG_STRIDE, this.seed, 0).then(
+      (r) => {
+        const m = this.metrics && this.metrics.blsThreadPool;
+        calls.forEach((c, ci) => {
+          if (r.groupResult[ci] !== 1) {
+            this.stats.sameMessageRetries++;
+            this.stats.sameMessageRetrySets += c.sets.length;
+            if (m && m.sameMessageRetryJobs) m.sameMessageRetryJobs.inc(1);
+            if (m && m.sameMessageRetrySets) m.sameMessageRetrySets.inc(c.sets.length);
+          }
+          c.resolve(Array.from(r.setResult.subarray(groupFirst[ci], groupFirst[ci + 1]), (x) => x === 1));
         });
       },
       (err) => {
@@ -612,5 +647,6 @@ module.exports = {
   MAX_JOBS_CAN_ACCEPT_WORK,
   JOB_BATCHABLE,
   JOB_URGENT,
+  SAME_LANE_FORMS,
   addon,
 };

@@ -33,6 +33,11 @@
  *       -> Promise<{outPk: Uint8Array, outSig: Uint8Array, status: Int8Array, firstBad: Uint32Array}>
  *     blsgpu_aggregate_with_randomness as napi_create_async_work, the same lifetime rules as aggregateSignatures
  *     (seed 0 = fresh scalars; a non-zero seed, an integer below 2^53, only for comparison runs).
+ *   verifySameMessage(ctx, groupFirst: Uint32Array, msgs: Uint8Array (32 bytes per group), pkBytes: Uint8Array | null,
+ *                     pkIndex: Uint32Array | null, sigs: Uint8Array, sigLen: Uint32Array, sigStride, seed, flags)
+ *       -> Promise<{setResult: Int8Array, groupResult: Int8Array, stats: {groupsAccepted, groupsRetried, retrySets,
+ *                   uniqueMessages, form, deviceMs}}>
+ *     blsgpu_verify_same_message as napi_create_async_work, the same lifetime rules as aggregateWithRandomness.
  *   debugInject(what, skip, count)                                blsgpu_debug_inject (only with BLSGPU_FAULT_INJECTION=1)
  */
 #define NAPI_VERSION 6
@@ -731,6 +736,164 @@ static napi_value AggregateWithRandomness(napi_env env, napi_callback_info info)
   return promise;
 }
 
+/* verifySameMessage: one blsgpu_verify_same_message call as async work (lifetimes as aggregateWithRandomness: every
+ * input is copied before the call returns, the outputs are the call's own until its completion on the main thread, and
+ * the context stays open while the call is pending -- close() waits for agg_pending) */
+typedef struct {
+  CtxBox* box;
+  uint32_t n_groups, n_sets, stride, flags;
+  uint64_t seed;
+  uint32_t* group_first;
+  uint8_t* msgs;
+  uint8_t* pk_bytes;
+  uint32_t* pk_index;
+  uint32_t* sig_len;
+  uint8_t* sigs;
+  int8_t* set_result;
+  int8_t* group_result;
+  blsgpu_same_message_stats stats;
+  int rc;
+  napi_deferred deferred;
+  napi_async_work work;
+} SameCall;
+
+static void same_free(SameCall* a) {
+  free(a->group_first);
+  free(a->msgs);
+  free(a->pk_bytes);
+  free(a->pk_index);
+  free(a->sig_len);
+  free(a->sigs);
+  free(a->set_result);
+  free(a->group_result);
+  free(a);
+}
+
+/* libuv worker thread */
+static void same_execute(napi_env env, void* data) {
+  (void)env;
+  SameCall* a = (SameCall*)data;
+  a->rc = blsgpu_verify_same_message(a->box->ctx, a->n_groups, a->group_first, a->msgs, a->pk_bytes, a->pk_index,
+                                     a->sigs, a->stride, a->sig_len, a->seed, a->flags, a->set_result, a->group_result,
+                                     &a->stats);
+}
+
+static void set_u32(napi_env env, napi_value obj, const char* key, uint32_t v) {
+  napi_value x;
+  napi_create_uint32(env, v, &x);
+  napi_set_named_property(env, obj, key, x);
+}
+
+/* JS main thread */
+static void same_complete(napi_env env, napi_status st, void* data) {
+  SameCall* a = (SameCall*)data;
+  a->box->agg_pending--;
+  if (st != napi_ok || a->rc != BLSGPU_OK) {
+    const char* name = blsgpu_code_name(st != napi_ok ? BLSGPU_ERR_CLOSED : a->rc);
+    napi_value msg, code, err;
+    napi_create_string_utf8(env, name ? name : "BLSGPU_DEVICE_ERROR", NAPI_AUTO_LENGTH, &msg);
+    napi_create_string_utf8(env, name ? name : "BLSGPU_DEVICE_ERROR", NAPI_AUTO_LENGTH, &code);
+    napi_create_error(env, code, msg, &err);
+    napi_reject_deferred(env, a->deferred, err);
+  } else {
+    napi_value out, stats, ms;
+    napi_create_object(env, &out);
+    napi_set_named_property(env, out, "setResult", copy_out(env, napi_int8_array, a->set_result, a->n_sets, 1));
+    napi_set_named_property(env, out, "groupResult", copy_out(env, napi_int8_array, a->group_result, a->n_groups, 1));
+    napi_create_object(env, &stats);
+    set_u32(env, stats, "groupsAccepted", a->stats.groups_accepted);
+    set_u32(env, stats, "groupsRetried", a->stats.groups_retried);
+    set_u32(env, stats, "retrySets", a->stats.retry_sets);
+    set_u32(env, stats, "uniqueMessages", a->stats.unique_messages);
+    set_u32(env, stats, "form", a->stats.form);
+    napi_create_double(env, a->stats.device_ms, &ms);
+    napi_set_named_property(env, stats, "deviceMs", ms);
+    napi_set_named_property(env, out, "stats", stats);
+    napi_resolve_deferred(env, a->deferred, out);
+  }
+  napi_delete_async_work(env, a->work);
+  same_free(a);
+}
+
+static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value argv[10];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 10) {
+    napi_throw_type_error(env, NULL,
+                          "verifySameMessage(ctx, groupFirst, msgs, pkBytes, pkIndex, sigs, sigLen, sigStride, seed, flags)");
+    return NULL;
+  }
+  CtxBox* box = get_open_box(env, argv[0]);
+  if (!box) return NULL;
+  size_t n_gf = 0, n_msg = 0, n_pkb = 0, n_pki = 0, n_bytes = 0, n_len = 0;
+  void *gf = NULL, *msgs = NULL, *pkb = NULL, *pki = NULL, *sigs = NULL, *slen = NULL;
+  if (opt_typed(env, argv[1], napi_uint32_array, &gf, &n_gf) || !gf ||
+      opt_typed(env, argv[2], napi_uint8_array, &msgs, &n_msg) || !msgs ||
+      opt_typed(env, argv[3], napi_uint8_array, &pkb, &n_pkb) ||
+      opt_typed(env, argv[4], napi_uint32_array, &pki, &n_pki) ||
+      opt_typed(env, argv[5], napi_uint8_array, &sigs, &n_bytes) || !sigs ||
+      opt_typed(env, argv[6], napi_uint32_array, &slen, &n_len) || !slen) {
+    napi_throw_type_error(env, NULL,
+                          "verifySameMessage: groupFirst, pkIndex, sigLen Uint32Array; msgs, pkBytes, sigs Uint8Array");
+    return NULL;
+  }
+  uint32_t stride = 0, flags = 0;
+  double seed = 0;
+  napi_get_value_uint32(env, argv[7], &stride);
+  napi_get_value_double(env, argv[8], &seed);
+  napi_get_value_uint32(env, argv[9], &flags);
+  /* shape checks on the host before anything is queued */
+  const uint32_t* gfw = (const uint32_t*)gf;
+  int ok = n_gf >= 1 && stride >= 96 && !(flags & ~BLSGPU_SAME_LANE_FORMS) && gfw[0] == 0 &&
+           (pkb != NULL) != (pki != NULL) && seed >= 0 && seed < 9007199254740992.0 && n_msg == 32 * (n_gf - 1);
+  for (size_t g = 0; ok && g + 1 < n_gf; g++) ok = gfw[g + 1] >= gfw[g];
+  ok = ok && gfw[n_gf - 1] == n_len && n_len <= (1u << 20) && n_bytes >= (size_t)stride * n_len;
+  ok = ok && (pkb ? n_pkb == 96 * n_len : n_pki == n_len);
+  for (size_t k = 0; ok && stride < 192 && k < n_len; k++) ok = ((const uint32_t*)slen)[k] != 192;
+  if (!ok) {
+    napi_throw_range_error(env, "BLSGPU_ERR_ARGS", "verifySameMessage: inconsistent array sizes");
+    return NULL;
+  }
+  SameCall* a = (SameCall*)calloc(1, sizeof(SameCall));
+  if (!a) {
+    napi_throw_error(env, NULL, "verifySameMessage: could not queue the call");
+    return NULL;
+  }
+  a->box = box;
+  a->n_groups = (uint32_t)n_gf - 1;
+  a->n_sets = (uint32_t)n_len;
+  a->stride = stride;
+  a->flags = flags;
+  a->seed = (uint64_t)seed;
+  a->group_first = (uint32_t*)dup_bytes(gf, n_gf * 4);
+  a->msgs = (uint8_t*)dup_bytes(msgs, n_msg);
+  if (pkb) a->pk_bytes = (uint8_t*)dup_bytes(pkb, n_pkb);
+  if (pki) a->pk_index = (uint32_t*)dup_bytes(pki, n_pki * 4);
+  a->sig_len = (uint32_t*)dup_bytes(slen, n_len * 4);
+  a->sigs = (uint8_t*)dup_bytes(sigs, (size_t)stride * n_len);
+  a->set_result = (int8_t*)calloc((size_t)n_len + 1, 1);
+  a->group_result = (int8_t*)calloc((size_t)a->n_groups + 1, 1);
+  napi_value promise, name;
+  if (!a->group_first || !a->msgs || (!a->pk_bytes && !a->pk_index) || !a->sig_len || !a->sigs || !a->set_result ||
+      !a->group_result || napi_create_promise(env, &a->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "blsgpu_verify_same_message", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, NULL, name, same_execute, same_complete, a, &a->work) != napi_ok) {
+    same_free(a);
+    napi_throw_error(env, NULL, "verifySameMessage: could not queue the call");
+    return NULL;
+  }
+  box->agg_pending++;
+  if (napi_queue_async_work(env, a->work) != napi_ok) {
+    box->agg_pending--;
+    napi_delete_async_work(env, a->work);
+    same_free(a);
+    napi_throw_error(env, NULL, "verifySameMessage: could not queue the call");
+    return NULL;
+  }
+  return promise;
+}
+
 /* debugInject(what, skip, count): blsgpu_debug_inject (test hook; BLSGPU_INJECT_ENTROPY 1, BLSGPU_INJECT_DEVICE 2) */
 static napi_value DebugInject(napi_env env, napi_callback_info info) {
   size_t argc = 3;
@@ -764,6 +927,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
       {"keyValidate", NULL, KeyValidate, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"aggregateSignatures", NULL, AggregateSignatures, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"aggregateWithRandomness", NULL, AggregateWithRandomness, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
+      {"verifySameMessage", NULL, VerifySameMessage, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   /* the fault-injection test hook is exported, by its own definition, only to processes started with

@@ -19,6 +19,27 @@ export type BlsGpuVerifierOpts = {
   groupPolicy?: 0 | 1;
   /** batch-scalar seed for comparison runs; 0 / undefined = OS CSPRNG */
   seed?: number;
+  /** true: a flush of same-message calls is one addon.verifySameMessage call per pubkey mode -- the aggregation, every
+   * aggregate's pairing check and the per-set retry of the groups that fail, without leaving the device (default
+   * false: an aggregation call, then verification jobs) */
+  fusedSameMessage?: boolean;
+};
+
+/** What addon.verifySameMessage resolves to (blsgpu_verify_same_message). */
+export type SameMessageResult = {
+  /** per set: 1 valid, 0 invalid, -code rejected */
+  setResult: Int8Array;
+  /** per group: 1 accepted as a whole, 0 verified set by set, -9 empty */
+  groupResult: Int8Array;
+  stats: {
+    groupsAccepted: number;
+    groupsRetried: number;
+    retrySets: number;
+    uniqueMessages: number;
+    /** bit 0: group phase took the lane forms, bit 1: retry phase did */
+    form: number;
+    deviceMs: number;
+  };
 };
 
 export type BlsGpuVerifierModules = {
@@ -57,7 +78,7 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
     /** same-message calls retried set by set, and their sets (blsThreadPool.sameMessageRetryJobs / ...Sets) */
     sameMessageRetries: number;
     sameMessageRetrySets: number;
-    /** device aggregateWithRandomness calls */
+    /** device aggregateWithRandomness calls (fusedSameMessage: verifySameMessage calls) */
     sameMessageAggregations: number;
     urgentCalls?: number;
   };
@@ -101,4 +122,6 @@ export declare const SignatureSetType: {single: "single"; aggregate: "aggregate"
 export declare const MAX_BUFFERED_SIGS: number;
 export declare const MAX_BUFFER_WAIT_MS: number;
 export declare const MAX_JOBS_CAN_ACCEPT_WORK: number;
+/** flags bit of addon.verifySameMessage: the large-call kernel forms whatever the size (diagnostics) */
+export declare const SAME_LANE_FORMS: number;
 export declare const addon: Record<string, (...args: unknown[]) => unknown>;

@@ -18,6 +18,7 @@ export const {
   SignatureSetType,
   MAX_BUFFERED_SIGS,
   MAX_BUFFER_WAIT_MS,
+  SAME_LANE_FORMS,
   addon,
 } = impl;
 export default impl;
