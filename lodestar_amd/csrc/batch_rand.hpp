@@ -102,7 +102,7 @@ inline Key seed_key(uint64_t seed) {
               0x2072616cu, 0x7379656bu}};
 }
 
-// The message index's hash key (runtime.cpp MsgIndex): 64 bits of the call key's own keystream under a separate nonce,
+// The message index's hash key (runtime_internal.hpp MsgIndex): 64 bits of the call key's own keystream under a separate nonce,
 // so no key word of the scalars' keystream ever drives the host hash table (a timing leak of the table would reveal
 // nothing about the scalars).
 inline uint64_t hash_key(const Key& key) {

@@ -1,0 +1,141 @@
+// Device-arena layouts of the synchronous helper calls (helpers.cpp): per call one struct of named offsets, computed
+// by its constructor from the call's sizes, fields in arena order.  No HIP here: tests/native/layout_probe.cpp includes
+// this header alone and tests/test_helper_layout.py compares every offset and total with the formulas in Python.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace helper_layout {
+
+// words per element, as kernels.h defines them (helpers.cpp asserts that the two agree)
+constexpr size_t kFp = 14, kG1A = 2 * kFp, kG1J = 3 * kFp, kG2A = 4 * kFp, kG2J = 6 * kFp, kFp12 = 12 * kFp;
+constexpr size_t kAwrTabWords = 9 * kG2J;              // window scratch per lane of the randomized sums
+constexpr size_t kMillerLineWords = 68 * 3 * 2 * kFp;  // stored Miller lines per message
+
+// Appends fields to an arena: take(size) returns the field's offset and moves on to the next multiple of `align`.
+// `end` is where the last field ends (the total of an arena with no padding after it), `at` that end rounded up.
+struct Carve {
+  size_t align = 256, at = 0, end = 0;
+  size_t take(size_t size) {
+    const size_t o = at;
+    end = o + size, at = (end + align - 1) / align * align;
+    return o;
+  }
+};
+
+// blsgpu_aggregate_pubkeys.  d_in: set_pk_first | keys | out | status.  d_work: a Jacobian sum per set.
+struct AggPubkeys {
+  size_t spf, keys, out, st, total, key_bytes, work_words;
+  AggPubkeys(size_t n, size_t npk, bool keys_are_bytes, size_t out_len) {
+    Carve c;
+    key_bytes = npk * (keys_are_bytes ? 96 : 4);
+    spf = c.take((n + 1) * 4), keys = c.take(key_bytes), out = c.take(n * out_len), st = c.take(3 * n);
+    total = c.end, work_words = n * kG1J;
+  }
+};
+
+// blsgpu_aggregate_signatures.  d_in: group_first | sig_len | sigs | out | first_bad | group status | signature
+// status | signature flags.  d_work: sig_aff | a Jacobian sum per group (w_agg).
+struct AggSigs {
+  size_t gf, len, sigs, out, fb, gst, st, fl, total, w_agg, work_words;
+  AggSigs(size_t G, size_t n, size_t sig_stride, size_t out_len) {
+    Carve c;
+    gf = c.take((G + 1) * 4), len = c.take(n * 4), sigs = c.take(n * sig_stride), out = c.take(G * out_len);
+    fb = c.take(G * 4), gst = c.take(G), st = c.take(n), fl = c.take(n), total = c.end;
+    w_agg = n * kG2A, work_words = w_agg + G * kG2J;
+  }
+};
+
+// What both same-message calls begin their d_in with: words | group_first | sig_len | sigs | keys.
+struct SameInput {
+  size_t words, gf, len, sigs, keys, key_bytes;
+  SameInput() {}
+  SameInput(Carve& c, size_t G, size_t n, size_t sig_stride, bool keys_are_bytes) {
+    key_bytes = n * (keys_are_bytes ? 96 : 4);
+    words = c.take(n * 8), gf = c.take((G + 1) * 4), len = c.take(n * 4), sigs = c.take(n * sig_stride);
+    keys = c.take(key_bytes);
+  }
+};
+
+// blsgpu_aggregate_with_randomness.  d_in: the shared inputs | out_pk | out_sig | first_bad | error indices | group
+// status | error codes | signature status | signature flags (the b_ fields are those hl::Same keeps in d_bytes).
+// d_work: sig_aff | window scratch | sum_pk | sum_sig.
+struct Awr {
+  SameInput in;
+  size_t opk, osig, fb, b_ek, gst, b_ec, b_st, b_fl, total;
+  size_t w_tab, w_sum_pk, w_sum_sig, work_words;
+  Awr(size_t G, size_t n, size_t sig_stride, bool keys_are_bytes, size_t out_pk_len, size_t out_sig_len,
+      size_t lanes) {
+    Carve c, w{1};
+    in = SameInput(c, G, n, sig_stride, keys_are_bytes);
+    opk = c.take(G * out_pk_len), osig = c.take(G * out_sig_len), fb = c.take(G * 4), b_ek = c.take(G * 8);
+    gst = c.take(G), b_ec = c.take(2 * G), b_st = c.take(n), b_fl = c.take(n), total = c.end;
+    w.take(n * kG2A);  // sig_aff, at 0
+    w_tab = w.take(lanes * kAwrTabWords), w_sum_pk = w.take(G * kG1J), w_sum_sig = w.take(G * kG2J);
+    work_words = w.end;
+  }
+};
+
+// blsgpu_verify_same_message, group phase (U unique messages).
+//   d_in:    the shared inputs | unique messages | group message indices | iota
+//   d_bytes: error indices | error codes | signature status | signature flags | message flags | group include |
+//            group code | group verdict | group_result | set_result
+//   d_work:  sig_aff | window scratch of the G2 sum | of the G1 sum | sum_pk | sum_sig | pk_aff | 1 / z | F | G |
+//            message branch (inv, h_aff, h_jac, h_norm, h_prep, h_q);  d_lines: the messages' Miller lines
+struct Same {
+  SameInput in;
+  size_t umsg, gmsg, iota, in_total;
+  size_t b_ek, b_ec, b_st, b_fl, b_mf, b_inc, b_code, b_ok, b_gres, b_sres, bytes_total;
+  size_t w_tab, w_tab_pk, w_sum_pk, w_sum_sig, w_pk_aff, w_inv, w_F, w_G;
+  size_t w_minv, w_haff, w_hjac, w_hnorm, w_hprep, w_hq, work_words, lines_words;
+  Same(size_t G, size_t n, size_t U, size_t sig_stride, bool keys_are_bytes, size_t lanes) {
+    Carve c, b, w{1};
+    in = SameInput(c, G, n, sig_stride, keys_are_bytes);
+    umsg = c.take(U * 32), gmsg = c.take(G * 4), iota = c.take((G + 1) * 4), in_total = c.at;
+    b_ek = b.take(G * 8), b_ec = b.take(2 * G), b_st = b.take(n), b_fl = b.take(n), b_mf = b.take(U);
+    b_inc = b.take(G), b_code = b.take(G), b_ok = b.take(G), b_gres = b.take(G), b_sres = b.take(n);
+    bytes_total = b.at;
+    w.take(n * kG2A);  // sig_aff, at 0
+    w_tab = w.take(lanes * kAwrTabWords), w_tab_pk = w.take(lanes * kAwrTabWords);
+    w_sum_pk = w.take(G * kG1J), w_sum_sig = w.take(G * kG2J), w_pk_aff = w.take(G * kG1A);
+    w_inv = w.take(G * kFp), w_F = w.take(G * kFp12), w_G = w.take(G * kFp12);
+    w_minv = w.take(U * kFp), w_haff = w.take(U * kG2A), w_hjac = w.take(U * kG2J), w_hnorm = w.take(U * kFp);
+    w_hprep = w.take(U * 14 * kFp), w_hq = w.take(U * 2 * kG2J);
+    work_words = w.end, lines_words = U * kMillerLineWords;
+  }
+};
+
+// blsgpu_verify_same_message, retry phase of nr sets.  d_list (words): list | message indices | iota.  d_ok (bytes):
+// include | code | verdict.  d_fb, d_S, d_F (and d_G): an affine key, a Jacobian signature, an Fp12 value per set.
+struct SameRetry {
+  size_t msg, iota, list_words, code, ok, ok_bytes, fb_words, S_words, F_words;
+  SameRetry(size_t nr) {
+    Carve c, b;
+    c.take(nr * 4);  // list, at 0
+    msg = c.take(nr * 4) / 4, iota = c.take((nr + 1) * 4) / 4, list_words = c.end / 4;
+    b.take(nr);  // include, at 0
+    code = b.take(nr), ok = b.take(nr), ok_bytes = b.at;
+    fb_words = nr * kG1A, S_words = nr * kG2J, F_words = nr * kFp12;
+  }
+};
+
+// blsgpu_key_validate.  d_in: keys | out (96 bytes each) | status.
+struct KeyValidate {
+  size_t keys, out, st, total;
+  KeyValidate(size_t n, size_t stride) {
+    Carve c;
+    keys = c.take(n * stride), out = c.take(n * 96), st = c.take(n), total = c.end;
+  }
+};
+
+// blsgpu_signing_roots.  d_in: objects | domains (one per object, or one for all when domain_stride is 0) | roots.
+struct SigningRoots {
+  size_t objects, dom, out, total, dom_bytes;
+  SigningRoots(size_t n, size_t object_stride, size_t domain_stride) {
+    Carve c;
+    dom_bytes = (domain_stride ? n : 1) * (domain_stride ? domain_stride : 32);
+    objects = c.take(n * object_stride), dom = c.take(dom_bytes), out = c.take(32 * n), total = c.end;
+  }
+};
+
+}  // namespace helper_layout

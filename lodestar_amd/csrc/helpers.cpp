@@ -1,0 +1,575 @@
+// The synchronous helper calls of libblsgpu (include/blsgpu.h): aggregation, same-message verification, key
+// validation, signing roots and the debug ops.  Each runs start to finish on device 0 under Device::helper_mu, on
+// table_stream, in Device::helper's buffers; helper_call is the envelope they share and helper_layout.hpp says where
+// every field of their device arenas lies.  The asynchronous verification pipeline is runtime.cpp.
+#include "helper_layout.hpp"
+#include "runtime_internal.hpp"
+
+using namespace blsgpu_rt;
+namespace hl = helper_layout;
+
+static_assert(hl::kFp == W_FP && hl::kG1A == W_G1A && hl::kG1J == W_G1J && hl::kG2A == W_G2A && hl::kG2J == W_G2J &&
+                  hl::kFp12 == W_FP12 && hl::kAwrTabWords == AWR_TAB_WORDS && hl::kMillerLineWords == kMillerLineWords,
+              "helper_layout.hpp restates the element widths of kernels.h");
+
+namespace {
+
+// The envelope of every helper call: registers the call with the context (BLSGPU_ERR_CLOSED once it is closing),
+// takes device 0's helper lock -- and its table lock, shared, when the call reads the pubkey table -- selects the
+// device and runs body(device), whose value is the call's.  A HIP failure anywhere inside is BLSGPU_DEVICE_ERROR.
+template <class Body>
+int helper_call(blsgpu_ctx* ctx, bool reads_table, Body body) {
+  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
+  struct Leave {
+    blsgpu_ctx* ctx;
+    ~Leave() { leave(ctx); }
+  } leave_on_exit{ctx};
+  Device& d = *ctx->devs[0];
+  try {
+    std::lock_guard<std::mutex> helper(d.helper_mu);
+    std::shared_lock<std::shared_mutex> tl(d.table_mu, std::defer_lock);
+    if (reads_table) tl.lock();
+    HIPCHK(hipSetDevice(d.id));
+    return body(d, d.helper, d.table_stream);
+  } catch (HipError&) {
+    return BLSGPU_DEVICE_ERROR;
+  }
+}
+
+// The grouped calls' inputs: signatures [group_first[g], group_first[g + 1]) form group g; the same-message calls
+// add one key per signature, bytes or table indices.
+struct Grouped {
+  uint32_t G;
+  const uint32_t* group_first;
+  const uint8_t* sigs;
+  uint32_t sig_stride;
+  const uint32_t* sig_len;
+  const uint8_t* pk_bytes = nullptr;
+  const uint32_t* pk_index = nullptr;
+  uint32_t n = 0;  // group_first[G], set by check_group_layout
+};
+
+// BLSGPU_OK and a.n, or BLSGPU_ERR_ARGS: group_first starts at 0 and never decreases, at most 2^20 signatures, and
+// no 192-byte signature under a stride below 192.
+int check_group_layout(Grouped& a) {
+  if (a.group_first[0] != 0) return BLSGPU_ERR_ARGS;
+  for (uint32_t g = 0; g < a.G; g++)
+    if (a.group_first[g + 1] < a.group_first[g]) return BLSGPU_ERR_ARGS;
+  a.n = a.group_first[a.G];
+  if (a.n > (1u << 20)) return BLSGPU_ERR_ARGS;
+  if (a.sig_stride < 192)
+    for (uint32_t k = 0; k < a.n; k++)
+      if (a.sig_len[k] == 192) return BLSGPU_ERR_ARGS;
+  return BLSGPU_OK;
+}
+
+// What both same-message calls refuse before anything is written or reaches the device: no entropy for the call's
+// scalars (else `words` and the message index's hash key) and, under the table lock, a table index past the table.
+int same_begin(const Device& d, const Grouped& a, uint64_t seed, std::vector<uint64_t>& words, uint64_t& hash_key) {
+  batch_rand::Key key;
+  if (!resolve_key(seed, key, hash_key)) return BLSGPU_ERR_ENTROPY;
+  words.resize(a.n);
+  batch_rand::words(key, 0, a.n, words.data());
+  if (a.pk_index)
+    for (uint32_t k = 0; k < a.n; k++)
+      if (a.pk_index[k] >= d.table_n) return BLSGPU_ERR_ARGS;
+  return BLSGPU_OK;
+}
+
+// Copies group_first | sig_len | sigs to the fields gf, len, sigs of layout `l` in d_in and describes the signatures to
+// the decode: points at the start of d_work, flags and status bytes where the caller says.
+template <class Layout>
+PipelineBuffers sig_inputs(Slot& sl, const Grouped& a, const Layout& l, uint8_t* flags, uint8_t* status,
+                           hipStream_t s) {
+  uint8_t* din = sl.d_in.p;
+  HIPCHK(hipMemcpyAsync(din + l.gf, a.group_first, (size_t)(a.G + 1) * 4, hipMemcpyHostToDevice, s));
+  if (a.n) {
+    HIPCHK(hipMemcpyAsync(din + l.len, a.sig_len, (size_t)a.n * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(din + l.sigs, a.sigs, (size_t)a.n * a.sig_stride, hipMemcpyHostToDevice, s));
+  }
+  PipelineBuffers pb{};
+  pb.n = a.n;
+  pb.sigs = din + l.sigs;
+  pb.sig_len = reinterpret_cast<uint32_t*>(din + l.len);
+  pb.sig_stride = a.sig_stride;
+  pb.sig_aff = sl.d_work.p;
+  pb.flags = flags;
+  pb.status = reinterpret_cast<int8_t*>(status);
+  return pb;
+}
+
+// The start both same-message calls share (`l`: hl::Awr or hl::Same): the inputs words | group_first | sig_len | sigs |
+// keys go to d_in, and the signature decode (pb) and the randomized sums (the value) are told where everything of
+// theirs lies: inputs in d_in, points, window scratch and sums in d_work, the b_ byte fields at `bytes`.
+template <class Layout>
+AwrBuffers same_inputs(Device& d, const Grouped& a, const Layout& l, uint8_t* bytes, const uint64_t* words,
+                       uint32_t lanes, hipStream_t s, PipelineBuffers& pb) {
+  uint8_t* din = d.helper.d_in.p;
+  uint32_t* w = d.helper.d_work.p;
+  pb = sig_inputs(d.helper, a, l.in, bytes + l.b_fl, bytes + l.b_st, s);
+  if (a.n) {
+    HIPCHK(hipMemcpyAsync(din + l.in.words, words, (size_t)a.n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(din + l.in.keys, a.pk_bytes ? (const void*)a.pk_bytes : (const void*)a.pk_index,
+                          l.in.key_bytes, hipMemcpyHostToDevice, s));
+  }
+  AwrBuffers ab{};
+  ab.n = a.n;
+  ab.n_groups = a.G;
+  ab.group_first = reinterpret_cast<uint32_t*>(din + l.in.gf);
+  ab.words = reinterpret_cast<uint64_t*>(din + l.in.words);
+  ab.pk_bytes = a.pk_bytes ? din + l.in.keys : nullptr;
+  ab.pk_index = a.pk_bytes ? nullptr : reinterpret_cast<uint32_t*>(din + l.in.keys);
+  ab.pk_table = d.table.p;
+  ab.pk_table_n = d.table_n;
+  ab.sig_aff = pb.sig_aff;
+  ab.sig_flags = pb.flags;
+  ab.sig_status = pb.status;
+  ab.tab = w + l.w_tab;
+  ab.tab_n = lanes;
+  ab.sum_pk = w + l.w_sum_pk;
+  ab.sum_sig = w + l.w_sum_sig;
+  ab.err_k = reinterpret_cast<uint32_t*>(bytes + l.b_ek);
+  ab.err_c = reinterpret_cast<int8_t*>(bytes + l.b_ec);
+  return ab;
+}
+
+}  // namespace
+
+extern "C" {
+
+int blsgpu_aggregate_pubkeys(blsgpu_ctx* ctx, const blsgpu_batch* b, uint8_t* out, uint32_t out_len,
+                             int8_t* status) {
+  if (!ctx || ctx->devs.empty() || !b || !out || !status || (out_len != 48 && out_len != 96)) return BLSGPU_ERR_ARGS;
+  const uint32_t n = b->n_sets;
+  if (n == 0) return BLSGPU_OK;
+  if (!b->pk_bytes && (!b->set_pk_first || !b->pk_index)) return BLSGPU_ERR_ARGS;
+  return helper_call(ctx, true, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    // (set_pk_first: a synthetic 1-key-per-set layout in single-key bytes mode)
+    std::vector<uint32_t> spf(n + 1);
+    for (uint32_t i = 0; i <= n; i++) spf[i] = b->set_pk_first ? b->set_pk_first[i] : i;
+    const uint32_t npk = spf[n];
+    if (!b->pk_bytes)
+      for (uint32_t k = 0; k < npk; k++)
+        if (b->pk_index[k] >= d.table_n) return BLSGPU_ERR_ARGS;
+    const hl::AggPubkeys l(n, npk, b->pk_bytes != nullptr, out_len);
+    sl.d_in.ensure(l.total);
+    sl.d_work.ensure(l.work_words);
+    uint8_t* din = sl.d_in.p;
+    HIPCHK(hipMemcpyAsync(din + l.spf, spf.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(din + l.keys, b->pk_bytes ? (const void*)b->pk_bytes : (const void*)b->pk_index,
+                          l.key_bytes, hipMemcpyHostToDevice, s));
+    PipelineBuffers pb{};
+    pb.n = n;
+    pb.set_pk_first = reinterpret_cast<uint32_t*>(din + l.spf);
+    pb.pk_bytes = b->pk_bytes ? din + l.keys : nullptr;
+    pb.pk_index = b->pk_bytes ? nullptr : reinterpret_cast<uint32_t*>(din + l.keys);
+    pb.pk_table = d.table.p;
+    pb.pk_table_n = d.table_n;
+    pb.pk_jac = sl.d_work.p;
+    pb.status = reinterpret_cast<int8_t*>(din + l.st);
+    launch_pk_aggregate(pb, n, s);
+    launch_pk_serialize(pb, n, din + l.out, out_len, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, din + l.out, (size_t)n * out_len, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, din + l.st, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSGPU_OK;
+  });
+}
+
+int blsgpu_aggregate_signatures(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
+                                const uint8_t* sigs, uint32_t sig_stride, const uint32_t* sig_len, uint32_t flags,
+                                uint8_t* out, uint32_t out_len, int8_t* status, uint32_t* first_bad) {
+  if (!ctx || ctx->devs.empty() || !group_first || !sigs || !sig_len || !out || !status) return BLSGPU_ERR_ARGS;
+  if ((out_len != 96 && out_len != 192) || sig_stride < 96 || (flags & ~BLSGPU_AGG_VALIDATE)) return BLSGPU_ERR_ARGS;
+  if (n_groups == 0) return BLSGPU_OK;
+  Grouped a{n_groups, group_first, sigs, sig_stride, sig_len};
+  if (int e = check_group_layout(a)) return e;
+  const uint32_t n = a.n, G = n_groups;
+  return helper_call(ctx, false, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    const hl::AggSigs l(G, n, sig_stride, out_len);
+    sl.d_in.ensure(l.total);
+    sl.d_work.ensure(l.work_words);
+    uint8_t* din = sl.d_in.p;
+    const PipelineBuffers pb = sig_inputs(sl, a, l, din + l.fl, din + l.st, s);
+    const uint32_t* d_first = reinterpret_cast<uint32_t*>(din + l.gf);
+    uint32_t* agg = sl.d_work.p + l.w_agg;
+    int8_t* d_gst = reinterpret_cast<int8_t*>(din + l.gst);
+    uint32_t* d_fb = reinterpret_cast<uint32_t*>(din + l.fb);
+    // small calls (the pool insert) take the cooperative subgroup check, as small verification runs do
+    launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, (flags & BLSGPU_AGG_VALIDATE) != 0);
+    launch_sig_aggregate(pb, d_first, G, n, agg, d_gst, d_fb, s);
+    launch_sig_agg_serialize(d_first, G, agg, d_gst, din + l.out, out_len, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, din + l.out, (size_t)G * out_len, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, din + l.gst, G, hipMemcpyDeviceToHost, s));
+    if (first_bad) HIPCHK(hipMemcpyAsync(first_bad, din + l.fb, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSGPU_OK;
+  });
+}
+
+uint32_t blsgpu_sig_agg_lanes(uint32_t n_groups, uint32_t n_sigs) { return sig_agg_lanes(n_groups, n_sigs); }
+
+int blsgpu_randomness_words(uint32_t n, uint64_t seed, uint64_t* words) {
+  if (n && !words) return BLSGPU_ERR_ARGS;
+  batch_rand::Key key;
+  uint64_t hash_key = 0;
+  if (!resolve_key(seed, key, hash_key)) return BLSGPU_ERR_ENTROPY;
+  batch_rand::words(key, 0, n, words);
+  return BLSGPU_OK;
+}
+
+int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
+                                     const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
+                                     uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed, uint8_t* out_pk,
+                                     uint32_t out_pk_len, uint8_t* out_sig, uint32_t out_sig_len, int8_t* status,
+                                     uint32_t* first_bad) {
+  if (!ctx || ctx->devs.empty() || !group_first || !sigs || !sig_len || !out_pk || !out_sig || !status)
+    return BLSGPU_ERR_ARGS;
+  if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
+  if ((out_pk_len != 48 && out_pk_len != 96) || (out_sig_len != 96 && out_sig_len != 192) || sig_stride < 96)
+    return BLSGPU_ERR_ARGS;
+  if (n_groups == 0) return BLSGPU_OK;
+  Grouped a{n_groups, group_first, sigs, sig_stride, sig_len, pk_bytes, pk_index};
+  if (int e = check_group_layout(a)) return e;
+  const uint32_t n = a.n, G = n_groups;
+  return helper_call(ctx, true, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    std::vector<uint64_t> words;
+    uint64_t hash_key = 0;
+    if (int e = same_begin(d, a, seed, words, hash_key)) return e;
+    const uint32_t L = awr_lanes(G, n), lanes = awr_launch_lanes(G, L);
+    const hl::Awr l(G, n, sig_stride, pk_bytes != nullptr, out_pk_len, out_sig_len, lanes);
+    sl.d_in.ensure(l.total);
+    sl.d_work.ensure(l.work_words);
+    uint8_t* din = sl.d_in.p;
+    PipelineBuffers pb;
+    const AwrBuffers ab = same_inputs(d, a, l, din, words.data(), lanes, s, pb);
+    int8_t* d_gst = reinterpret_cast<int8_t*>(din + l.gst);
+    uint32_t* d_fb = reinterpret_cast<uint32_t*>(din + l.fb);
+    // small calls take the cooperative subgroup check, as small verification runs do
+    launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, true);
+    launch_awr_sums(ab, L, s);
+    launch_awr_serialize(ab, din + l.opk, out_pk_len, din + l.osig, out_sig_len, d_gst, d_fb, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_pk, din + l.opk, (size_t)G * out_pk_len, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out_sig, din + l.osig, (size_t)G * out_sig_len, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, din + l.gst, G, hipMemcpyDeviceToHost, s));
+    if (first_bad) HIPCHK(hipMemcpyAsync(first_bad, din + l.fb, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSGPU_OK;
+  });
+}
+
+uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets) { return awr_lanes(n_groups, n_sets); }
+
+// ---- one-call same-message verification ------------------------------------------------------------------------
+// A phase of at most kSameCoopMax pairings takes the cooperative kernels (a workgroup per Miller loop and per check:
+// latency), a larger one the lane forms (throughput).  512 is option "coop_max"'s default, taken as a constant: the
+// helper calls read no option.
+constexpr uint32_t kSameCoopMax = 512;
+uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags) {
+  return (flags & BLSGPU_SAME_LANE_FORMS) || n_items > kSameCoopMax ? 1u : 0u;
+}
+namespace {
+// diagnostics (tools/bench_same_message.py): the three branches of the group phase on one stream
+inline bool same_serial() {
+  static const bool on = [] {
+    const char* v = getenv("BLSGPU_SAME_SERIAL");
+    return v && v[0] == '1';
+  }();
+  return on;
+}
+// Miller values and checks of one phase: item i < n_items pairs pk_aff[i] (W_G1A, stride n_items) with H(msg_idx[i]) when
+// include[i], and ok[i] = FinalExp(F_i * MillerLoop(-g1, S_i)) == 1 with S (W_G2J, stride n_items).  iota = 0, 1, ..,
+// n_items: one item per Miller chunk.  Cooperative form: k_miller_coop and k_group_check with its own Miller loop.
+// Lane form: the messages' stored lines (pm.lines), k_miller_acc6 (six lanes per pairing), MillerLoop(-g1, S) on one
+// lane per item and the final exponentiation on six (k_group_check6).
+void same_pairing_phase(const PipelineBuffers& pm, uint32_t n_items, const uint32_t* iota, uint32_t* pk_aff,
+                        uint8_t* include, const uint32_t* msg_idx, const uint32_t* S, uint32_t* F, uint32_t* Gs,
+                        uint8_t* ok, bool lane, hipStream_t s) {
+  PipelineBuffers pb = pm;
+  pb.n = n_items;
+  pb.pk_aff = pk_aff;
+  pb.include = include;
+  pb.msg_idx = msg_idx;
+  pb.n_chunks = n_items;
+  pb.chunk_first = iota;
+  pb.chunk_items = iota;
+  pb.f_chunk = F;
+  if (!lane) {
+    launch_miller_coop(pb, false, s, false);
+    launch_group_check(S, F, n_items, ok, s);
+  } else {
+    launch_miller_acc6(pb, false, s);
+    launch_group_sig_miller(S, n_items, Gs, s, false, true);
+    launch_group_check6(F, Gs, n_items, ok, s);
+  }
+}
+}  // namespace
+
+int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first, const uint8_t* msgs,
+                               const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
+                               uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed, uint32_t flags,
+                               int8_t* set_result, int8_t* group_result, blsgpu_same_message_stats* stats) {
+  if (!ctx || ctx->devs.empty() || !group_first || !msgs || !sigs || !sig_len || !set_result) return BLSGPU_ERR_ARGS;
+  if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
+  if (sig_stride < 96 || (flags & ~BLSGPU_SAME_LANE_FORMS)) return BLSGPU_ERR_ARGS;
+  if (n_groups == 0) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    return BLSGPU_OK;
+  }
+  Grouped a{n_groups, group_first, sigs, sig_stride, sig_len, pk_bytes, pk_index};
+  if (int e = check_group_layout(a)) return e;
+  const uint32_t n = a.n, G = n_groups;
+  std::vector<int8_t> h_set(n), h_grp(G);
+  blsgpu_same_message_stats st;
+  memset(&st, 0, sizeof st);
+  const int rc = helper_call(ctx, true, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    std::vector<uint64_t> words;
+    uint64_t hash_key = 0;
+    if (int e = same_begin(d, a, seed, words, hash_key)) return e;
+    // messages, deduplicated as run_shard does: group g signs unique message gmsg[g]
+    std::vector<uint32_t> gmsg(G), uniq;
+    {
+      MsgIndex mi(G, hash_key ^ 0x6a09e667f3bcc908ull);
+      for (uint32_t g = 0; g < G; g++) gmsg[g] = mi.find_or_add(msgs, g, uniq);
+    }
+    const uint32_t U = (uint32_t)uniq.size();
+    st.unique_messages = U;
+    bool streams_used = false;
+    try {
+      if (!d.same_st[0]) {
+        for (auto& e : d.same_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIPCHK(hipStreamCreateWithFlags(&d.same_st[1], hipStreamNonBlocking));
+        HIPCHK(hipStreamCreateWithFlags(&d.same_st[0], hipStreamNonBlocking));
+      }
+      const auto t0 = std::chrono::steady_clock::now();
+      const bool serial = same_serial();
+      hipStream_t sb = serial ? s : d.same_st[0], sc = serial ? s : d.same_st[1];
+      const bool lane_g = blsgpu_same_message_form(G, flags) != 0;
+      const uint32_t L = awr_lanes(G, n), lanes = awr_launch_lanes(G, L);
+      const hl::Same l(G, n, U, sig_stride, pk_bytes != nullptr, lanes);
+      // every buffer of the group phase grows here, while none of the three streams has work (each call ends with all
+      // of them synchronized); the retry phase grows only buffers the group phase does not use, after its synchronize
+      sl.d_in.ensure(l.in_total);
+      sl.d_bytes.ensure(l.bytes_total);
+      sl.d_work.ensure(l.work_words);
+      if (lane_g) sl.d_lines.ensure(l.lines_words);
+      streams_used = true;
+      uint8_t* din = sl.d_in.p;
+      uint8_t* db = sl.d_bytes.p;
+      uint32_t* w = sl.d_work.p;
+      std::vector<uint32_t> iota((size_t)G + 1);
+      for (uint32_t g = 0; g <= G; g++) iota[g] = g;
+      std::vector<uint8_t> umsgs((size_t)U * 32);
+      for (uint32_t u = 0; u < U; u++) memcpy(umsgs.data() + (size_t)u * 32, msgs + (size_t)uniq[u] * 32, 32);
+      PipelineBuffers pb;  // the signature decode
+      const AwrBuffers ab = same_inputs(d, a, l, db, words.data(), lanes, s, pb);
+      HIPCHK(hipMemcpyAsync(din + l.umsg, umsgs.data(), (size_t)U * 32, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(din + l.gmsg, gmsg.data(), (size_t)G * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(din + l.iota, iota.data(), (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
+      AwrBuffers ab_pk = ab;  // the G1 sum runs beside the G2 sum: its own window scratch
+      ab_pk.tab = w + l.w_tab_pk;
+      uint32_t* g_pk_aff = w + l.w_pk_aff;
+      uint32_t* g_inv = w + l.w_inv;
+      uint32_t* g_F = w + l.w_F;
+      uint32_t* g_G = w + l.w_G;
+      PipelineBuffers pm{};  // the message branch
+      pm.umsgs = din + l.umsg;
+      pm.n_umsg = U;
+      pm.nm = U;
+      pm.inv_buf = w + l.w_minv;
+      pm.h_aff = w + l.w_haff;
+      pm.h_jac = w + l.w_hjac;
+      pm.h_norm = w + l.w_hnorm;
+      pm.h_prep = w + l.w_hprep;
+      pm.h_q = w + l.w_hq;
+      pm.mflags = db + l.b_mf;
+      pm.lines = sl.d_lines.p;
+      uint8_t* g_inc = db + l.b_inc;
+      int8_t* g_code = reinterpret_cast<int8_t*>(db + l.b_code);
+      uint8_t* g_ok = db + l.b_ok;
+      int8_t* d_gres = reinterpret_cast<int8_t*>(db + l.b_gres);
+      int8_t* d_sres = reinterpret_cast<int8_t*>(db + l.b_sres);
+      const uint32_t* d_gmsg = reinterpret_cast<uint32_t*>(din + l.gmsg);
+      const uint32_t* d_iota = reinterpret_cast<uint32_t*>(din + l.iota);
+      // ---- group phase: three branches from the input copy, joined into s
+      HIPCHK(hipEventRecord(d.same_ev[0], s));
+      if (!serial) {
+        HIPCHK(hipStreamWaitEvent(sb, d.same_ev[0], 0));
+        HIPCHK(hipStreamWaitEvent(sc, d.same_ev[0], 0));
+      }
+      // (a) signatures: decode + subgroup check (cooperative for small calls, as small verification runs), S_g
+      launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, true);
+      launch_awr_sum_sig(ab, L, s);
+      // (b) keys: P_g and the batch inverses of its z
+      launch_awr_sum_pk(ab_pk, L, sb);
+      launch_batch_inv(ab.sum_pk, G, 2 * W_FP, g_inv, G, sb);
+      HIPCHK(hipEventRecord(d.same_ev[1], sb));
+      // (c) messages: H(m) affine, and in the lane form its Miller lines
+      bool have_lines = false;
+      launch_hash_to_g2(pm, sc, U <= 4096, false);
+      launch_h_affine(pm, sc);
+      if (lane_g) {
+        launch_miller_lines2(pm, sc);
+        have_lines = true;
+      }
+      HIPCHK(hipEventRecord(d.same_ev[2], sc));
+      if (!serial) {
+        HIPCHK(hipStreamWaitEvent(s, d.same_ev[1], 0));
+        HIPCHK(hipStreamWaitEvent(s, d.same_ev[2], 0));
+      }
+      launch_same_group_items(ab, g_inv, g_pk_aff, g_inc, g_code, s);
+      same_pairing_phase(pm, G, d_iota, g_pk_aff, g_inc, d_gmsg, ab.sum_sig, g_F, g_G, g_ok, lane_g, s);
+      launch_same_group_results(ab.group_first, G, n, g_inc, g_code, g_ok, d_sres, d_gres, s);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(h_grp.data(), d_gres, G, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
+      if (lane_g) st.form |= 1;
+      // ---- retry phase: every set of a non-empty group whose check did not hold, on its own with r = 1
+      std::vector<uint32_t> rlist, rmsg, riota;  // (alive until the final synchronize: they are copied from)
+      for (uint32_t g = 0; g < G; g++) {
+        if (group_first[g + 1] == group_first[g]) continue;
+        if (h_grp[g] == 1) {
+          st.groups_accepted++;
+          continue;
+        }
+        st.groups_retried++;
+        for (uint32_t k = group_first[g]; k < group_first[g + 1]; k++) {
+          rlist.push_back(k);
+          rmsg.push_back(gmsg[g]);
+        }
+      }
+      const uint32_t nr = (uint32_t)rlist.size();
+      st.retry_sets = nr;
+      if (nr) {
+        const bool lane_r = blsgpu_same_message_form(nr, flags) != 0;
+        const hl::SameRetry r(nr);
+        sl.d_list.ensure(r.list_words);
+        sl.d_ok.ensure(r.ok_bytes);
+        sl.d_fb.ensure(r.fb_words);
+        sl.d_S.ensure(r.S_words);
+        sl.d_F.ensure(r.F_words);
+        if (lane_r) sl.d_G.ensure(r.F_words);
+        if (lane_r && !have_lines) {
+          sl.d_lines.ensure(l.lines_words);
+          pm.lines = sl.d_lines.p;
+        }
+        riota.resize((size_t)nr + 1);
+        for (uint32_t q = 0; q <= nr; q++) riota[q] = q;
+        uint32_t* dl = sl.d_list.p;
+        HIPCHK(hipMemcpyAsync(dl, rlist.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dl + r.msg, rmsg.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dl + r.iota, riota.data(), (size_t)(nr + 1) * 4, hipMemcpyHostToDevice, s));
+        uint8_t* r_inc = sl.d_ok.p;
+        int8_t* r_code = reinterpret_cast<int8_t*>(sl.d_ok.p + r.code);
+        uint8_t* r_ok = sl.d_ok.p + r.ok;
+        launch_same_retry_items(ab, dl, nr, sl.d_fb.p, sl.d_S.p, r_inc, r_code, s);
+        if (lane_r && !have_lines) launch_miller_lines2(pm, s);
+        same_pairing_phase(pm, nr, dl + r.iota, sl.d_fb.p, r_inc, dl + r.msg, sl.d_S.p, sl.d_F.p, sl.d_G.p, r_ok, lane_r,
+                           s);
+        launch_same_retry_results(dl, nr, r_inc, r_code, r_ok, d_sres, s);
+        HIPCHK(hipGetLastError());
+        if (lane_r) st.form |= 2;
+      }
+      if (n) HIPCHK(hipMemcpyAsync(h_set.data(), d_sres, n, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      st.device_ms = ms_since(t0);
+    } catch (HipError&) {
+      // no branch may outlive the call: the next helper call reuses, and may grow, the buffers they work on
+      if (streams_used) {
+        (void)hipStreamSynchronize(d.table_stream);
+        for (hipStream_t x : d.same_st)
+          if (x) (void)hipStreamSynchronize(x);
+      }
+      throw;
+    }
+    return BLSGPU_OK;
+  });
+  if (rc == BLSGPU_OK) {  // results reach the caller only when every one of them was computed
+    if (n) memcpy(set_result, h_set.data(), n);
+    if (group_result) memcpy(group_result, h_grp.data(), G);
+    if (stats) *stats = st;
+  }
+  return rc;
+}
+
+int blsgpu_key_validate(blsgpu_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_t pk_len, uint32_t stride,
+                        uint8_t* out96, int8_t* status) {
+  if (!ctx || ctx->devs.empty() || !pks || !status || stride < pk_len) return BLSGPU_ERR_ARGS;
+  if (pk_len != 48 && pk_len != 96) return BLSGPU_ERR_ARGS;
+  if (n == 0) return BLSGPU_OK;
+  return helper_call(ctx, false, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    const hl::KeyValidate l(n, stride);
+    sl.d_in.ensure(l.total);
+    uint8_t* din = sl.d_in.p;
+    HIPCHK(hipMemcpyAsync(din, pks, (size_t)n * stride, hipMemcpyHostToDevice, s));
+    launch_key_validate(din, n, pk_len, stride, din + l.out, reinterpret_cast<int8_t*>(din + l.st), s);
+    HIPCHK(hipGetLastError());
+    if (out96) HIPCHK(hipMemcpyAsync(out96, din + l.out, (size_t)n * 96, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, din + l.st, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSGPU_OK;
+  });
+}
+
+int blsgpu_signing_roots(blsgpu_ctx* ctx, int kind, uint32_t n, const uint8_t* objects, uint32_t object_stride,
+                         const uint8_t* domains, uint32_t domain_stride, uint8_t* out32) {
+  if (!ctx || ctx->devs.empty() || !objects || !domains || !out32) return BLSGPU_ERR_ARGS;
+  const uint32_t obj_len = kind == BLSGPU_ROOT_OBJECT ? 32 : (kind == BLSGPU_ROOT_ATTESTATION_DATA ? 128 : 0);
+  if (!obj_len || object_stride < obj_len || (domain_stride != 0 && domain_stride < 32)) return BLSGPU_ERR_ARGS;
+  if (n == 0) return BLSGPU_OK;
+  return helper_call(ctx, false, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    const hl::SigningRoots l(n, object_stride, domain_stride);
+    sl.d_in.ensure(l.total);
+    uint8_t* din = sl.d_in.p;
+    HIPCHK(hipMemcpyAsync(din, objects, (size_t)n * object_stride, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(din + l.dom, domains, l.dom_bytes, hipMemcpyHostToDevice, s));
+    launch_signing_roots(kind, din, n, object_stride, din + l.dom, domain_stride, din + l.out, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out32, din + l.out, 32 * (size_t)n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSGPU_OK;
+  });
+}
+
+int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint32_t in_stride, uint8_t* out,
+                    uint32_t out_stride, int32_t* status) {
+  if (!ctx || ctx->devs.empty() || !in || !out || !status) return BLSGPU_ERR_ARGS;
+  // the bytes each op reads per element and writes per element (k_debug.hip): a smaller stride is refused here, so a
+  // test hook can never read or write past its buffers on the device
+  struct OpSize {
+    int op;
+    uint32_t in, out;
+  };
+  static const OpSize kOpSizes[] = {{0, 96, 48},    {1, 194, 192},  {2, 32, 192},   {3, 288, 576},  {4, 576, 576},
+                                    {5, 104, 96},   {6, 200, 192},  {7, 64, 96},    {8, 32, 96},    {9, 200, 2880},
+                                    {10, 104, 1440}, {11, 840, 56}, {16, 576, 576}, {17, 288, 576}, {18, 384, 192}};
+  const OpSize* sz = nullptr;
+  for (const OpSize& o : kOpSizes)
+    if (o.op == op) sz = &o;
+  if (!sz || in_stride < sz->in || out_stride < sz->out) return BLSGPU_ERR_ARGS;
+  if (n == 0) return BLSGPU_OK;
+  return helper_call(ctx, false, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    struct Temp {  // its own allocations, not the helper's arenas: freed however the call ends
+      void* p = nullptr;
+      ~Temp() {
+        if (p) (void)hipFree(p);
+      }
+    } din, dout, dst;
+    HIPCHK(hipMalloc(&din.p, (size_t)n * in_stride));
+    HIPCHK(hipMalloc(&dout.p, (size_t)n * out_stride));
+    HIPCHK(hipMalloc(&dst.p, (size_t)n * 4));
+    HIPCHK(hipMemcpyAsync(din.p, in, (size_t)n * in_stride, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(dout.p, 0, (size_t)n * out_stride, s));
+    launch_debug_op(op, n, (uint8_t*)din.p, in_stride, (uint8_t*)dout.p, out_stride, (int32_t*)dst.p, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * out_stride, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(status, dst.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSGPU_OK;
+  });
+}
+
+}  // extern "C"

@@ -18,347 +18,25 @@
 //     group on its own (the reference re-verifies each job of a failed chunk, worker.ts:76-98): per job the
 //     answer is the reference's, valid iff every set of the job verifies.
 // There is no CPU verification path: without a usable GPU blsgpu_init fails.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <pthread.h>
+#include <stdio.h>
 #include <sys/random.h>
 
-#include <algorithm>
 #include <cmath>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <deque>
-#include <mutex>
-#include <shared_mutex>
 #include <string>
 #include <system_error>
-#include <thread>
-#include <vector>
 
-#include "../../include/blsgpu.h"
-#include "batch_rand.hpp"
-#include "kernels.h"
+#include "runtime_internal.hpp"
+
+using namespace blsgpu_rt;
 
 namespace {
-
-struct HipError {
-  hipError_t e;
-};
-#define HIPCHK(x)                             \
-  do {                                        \
-    hipError_t _e = (x);                      \
-    if (_e != hipSuccess) throw HipError{_e}; \
-  } while (0)
-
-// Device buffer that only grows.  A slot's buffers grow stream-ordered (hipFreeAsync / hipMallocAsync on the
-// slot's stream): a plain hipFree waits for the whole device, so a merged run larger than any before would stall
-// every other slot's work (seen as 1.4-2.5 s call latencies in the bench's tail).  Growth doubles.
-// growths of stream-ordered slot buffers by this thread (run_shard: an input copy may leave the run's stream only when
-// no buffer of the run was (re)allocated in that stream's order)
-thread_local uint64_t tl_async_grow = 0;
-// Diagnostics (BLSGPU_POISON=1 in the environment): every (re)allocated device buffer is filled with 0xA5 bytes before
-// first use, so a kernel that reads memory no kernel of its run wrote fails every time instead of only when the
-// allocator hands it memory another run left with different contents.
-inline bool poison_buffers() {
-  static const bool on = [] {
-    const char* v = getenv("BLSGPU_POISON");
-    return v && v[0] == '1';
-  }();
-  return on;
-}
-// Diagnostics (BLSGPU_SYNC_GROW=1): buffer growth with a whole-device synchronisation and plain hipFree / hipMalloc
-// instead of stream-ordered hipFreeAsync / hipMallocAsync.
-inline bool sync_grow() {
-  static const bool on = [] {
-    const char* v = getenv("BLSGPU_SYNC_GROW");
-    return v && v[0] == '1';
-  }();
-  return on;
-}
-// Every growth and release of a stream-ordered slot buffer holds this lock: the dispatcher threads of a device's slots
-// (and of every device) grow their buffers at the same moments -- a fresh process's first runs, and whenever the run
-// shapes change -- and the stream-ordered pool is then entered from several threads at once.  Growth is rare (buffers
-// only double), so the lock costs nothing measurable.  BLSGPU_GROW_UNLOCKED=1 (diagnostics) leaves it out.
-std::mutex g_grow_mu;
-inline bool grow_unlocked() {
-  static const bool on = [] {
-    const char* v = getenv("BLSGPU_GROW_UNLOCKED");
-    return v && v[0] == '1';
-  }();
-  return on;
-}
-// Diagnostics (BLSGPU_FB_VERIFY=1): every fallback of small jobs is re-computed and compared (run_shard)
-inline bool fb_verify() {
-  static const bool on = [] {
-    const char* v = getenv("BLSGPU_FB_VERIFY");
-    return v && v[0] == '1';
-  }();
-  return on;
-}
-inline bool grow_free() {
-  static const bool on = [] {
-    const char* v = getenv("BLSGPU_GROW_FREE");
-    return v && v[0] == '1';
-  }();
-  return on;
-}
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  hipStream_t st = nullptr;  // set for slot buffers
-  std::vector<T*> retired;   // outgrown stream-ordered blocks, freed with the buffer (ensure)
-  void ensure(size_t n) {
-    if (n <= cap) return;
-    std::unique_lock<std::mutex> lk(g_grow_mu, std::defer_lock);
-    if (!grow_unlocked()) lk.lock();
-    const size_t c = std::max<size_t>(n, cap * 2);
-    if (st && sync_grow()) {
-      HIPCHK(hipDeviceSynchronize());
-      if (p) HIPCHK(hipFree(p));
-      p = nullptr;
-      HIPCHK(hipMalloc((void**)&p, c * sizeof(T)));
-      if (poison_buffers()) HIPCHK(hipMemset(p, 0xA5, c * sizeof(T)));
-      HIPCHK(hipDeviceSynchronize());
-      tl_async_grow++;
-    } else if (st) {
-      // the outgrown block is kept until the buffer is released instead of going back to the stream-ordered pool at
-      // once (BLSGPU_GROW_FREE=1: freed at once, as before): with the adaptive group sizes, whose buffer shapes change
-      // over a fresh process's first runs, the kept per-set Miller values (run_shard keep_f) were found overwritten in
-      // ~6% of fresh C5 processes.  Growth doubles, so the kept blocks add up to less than the buffer.
-      if (p && grow_free()) HIPCHK(hipFreeAsync(p, st));
-      else if (p) retired.push_back(p);
-      p = nullptr;
-      HIPCHK(hipMallocAsync((void**)&p, c * sizeof(T), st));
-      if (poison_buffers()) HIPCHK(hipMemsetAsync(p, 0xA5, c * sizeof(T), st));
-      tl_async_grow++;
-    } else {
-      if (p) HIPCHK(hipFree(p));
-      p = nullptr;
-      HIPCHK(hipMalloc((void**)&p, c * sizeof(T)));
-      if (poison_buffers()) {  // the fill is on the null stream: complete it before any stream uses the buffer
-        HIPCHK(hipMemset(p, 0xA5, c * sizeof(T)));
-        HIPCHK(hipStreamSynchronize(nullptr));
-      }
-    }
-    cap = c;
-  }
-  void release() {
-    std::unique_lock<std::mutex> lk(g_grow_mu, std::defer_lock);
-    if (!grow_unlocked()) lk.lock();
-    if (p) (void)(st ? hipFreeAsync(p, st) : hipFree(p));
-    for (T* q : retired) (void)(st ? hipFreeAsync(q, st) : hipFree(q));
-    retired.clear();
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-template <class T>
-struct HostBuf {  // pinned staging
-  T* p = nullptr;
-  size_t cap = 0;
-  void ensure(size_t n) {
-    if (n <= cap) return;
-    std::unique_lock<std::mutex> lk(g_grow_mu, std::defer_lock);
-    if (!grow_unlocked()) lk.lock();
-    if (p) HIPCHK(hipHostFree(p));
-    p = nullptr;
-    size_t c = std::max<size_t>(n, cap * 2);
-    HIPCHK(hipHostMalloc((void**)&p, c * sizeof(T), hipHostMallocDefault));
-    if (poison_buffers()) memset(p, 0x5A, c * sizeof(T));
-    cap = c;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-constexpr int kStages = 8;
-constexpr size_t kMillerLineWords = (size_t)MILLER_STEPS * W_LINE;
-
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// One runtime slot: a dispatcher's staging and work buffers and its events.  The pipeline streams belong to the device
-// (Device::st) and are shared by its slots; each slot adds its own fallback stream (Slot::fb).  Under HIP's default of
-// 4 hardware queues a process's streams share queues (HIP deals streams over its queues), so a fallback stream may
-// share a queue with a pipeline stream; CU-masked streams (urgent partition, create_streams) get queues of their own.
-struct Slot {
-  hipEvent_t join_in = nullptr, join_msg = nullptr, join_pk = nullptr, join_mask = nullptr, join_gsm = nullptr,
-             join_dec = nullptr, join_msm = nullptr, join_rsig = nullptr, done = nullptr;  // no timing
-  hipEvent_t ev[2 * (kStages + 2)] = {};  // profile: (start, end) per stage; pairs kStages, kStages + 1 = the
-                                          // Miller lines, the groups' MillerLoop(-g1, S) (parts of stages 5, 7)
-  // d_in / h_in: every per-call input packed into one arena (one H2D transfer); d_res / h_res: job errors +
-  // group verdicts (one D2H transfer).
-  DevBuf<uint8_t> d_in, d_res, d_bytes, d_ok, d_fbflags;
-  DevBuf<uint32_t> d_work, d_lines, d_S, d_F, d_G, d_list, d_msmB, d_msmW, d_fb;
-  DevBuf<uint32_t> d_fkeep;  // the batch pass's per-set Miller values, kept for the fallback (run_shard keep_f)
-  HostBuf<uint8_t> h_in, h_res, h_ok;
-  HostBuf<uint32_t> h_list;
-  // The slot's own stream for the fallback of its runs (lowest priority).  A failed group's checks used to run on the
-  // run's signature stream, shared by every run of that stream pair: under load (C5, 1% invalid) a 3,424-check launch
-  // held that stream 33-46 ms and the next runs' decodes and MSMs queued behind it (r05 trace).
-  hipStream_t fb = nullptr;
-  bool retire = false;     // set under the device queue lock: the dispatcher exits instead of taking work
-  bool in_flight = false;  // the slot's run counts in Device::runs_inflight
-  bool alone = false;      // no other run was in flight when the slot took its run
-  bool urgent = false;     // the device's urgent-lane slot (BLSGPU_JOB_URGENT calls): its own streams (Device::ust)
-
-  // the stream buffer growth is ordered on (hipFreeAsync / hipMallocAsync); the slot's previous work is complete
-  // whenever it grows a buffer (its dispatcher waits for each run), so only this ordering matters
-  void set_stream(hipStream_t st) {
-    for (auto* b : {&d_in, &d_res, &d_bytes, &d_ok, &d_fbflags}) b->st = st;
-    for (auto* b : {&d_work, &d_lines, &d_S, &d_F, &d_G, &d_list, &d_msmB, &d_msmW, &d_fb, &d_fkeep}) b->st = st;
-  }
-  void release_all() {
-    d_in.release(); d_res.release(); d_bytes.release(); d_ok.release(); d_fbflags.release();
-    d_work.release(); d_lines.release(); d_S.release(); d_F.release(); d_list.release();
-    d_msmB.release(); d_msmW.release(); d_fb.release(); d_G.release(); d_fkeep.release();
-    h_in.release(); h_res.release(); h_ok.release(); h_list.release();
-  }
-};
-
-struct Call;
-struct Task {
-  Call* call;
-  uint32_t shard;
-};
-
-// The device's pipeline streams, shared by its slots: one per branch of a run's DAG (run_shard).  Runs of different
-// slots queue behind each other per branch, so the chip always has the next run's work while one run's tail drains.
-enum { kSig = 0, kMsg = 1, kPk = 2, kTail = 3, kStreams = 4, kMaxPairs = 3 };
-// streams created with the device's highest priority (bit k = stream k); see blsgpu_init
-#ifndef BLSGPU_STREAM_PRIO
-#define BLSGPU_STREAM_PRIO ((1 << kMsg) | (1 << kTail))
-#endif
-// Stream pairs (default): consecutive runs alternate between two (signature, message) stream pairs -- run parity p
-// uses st[2p] for its signature, pubkey and tail branches and st[2p + 1] (high priority) for its message branch --
-// so the message chains of the two runs in flight (pipeline_depth 2) overlap instead of queueing behind each other on
-// one message stream, the serial chain that bounded throughput.  0: one stream per branch, shared by all runs.
-#ifndef BLSGPU_STREAM_PAIRS
-#define BLSGPU_STREAM_PAIRS 1
-#endif
-
-
-struct Device {
-  int id = 0;
-  hipStream_t table_stream = nullptr;  // uploads and the synchronous helpers (debug, aggregate, ...)
-  hipStream_t st[2 * kMaxPairs] = {};
-  int npairs = 2;  // stream pairs in use: 3 when the process has >= 6 hardware queues (a pair per slot)
-  std::mutex enq_mu;  // one run's batch (or fallback) launches are enqueued without another slot's in between
-  std::mutex helper_mu;
-  Slot helper;  // buffers of the synchronous helpers (on table_stream)
-  // blsgpu_verify_same_message (under helper_mu): the streams of its key-sum and message branches and the events that
-  // join them into table_stream, created by the first such call
-  hipStream_t same_st[2] = {};
-  hipEvent_t same_ev[3] = {};
-  // pubkey table (AoS, W_PKTAB words per key): verification holds it shared, uploads exclusive
-  std::shared_mutex table_mu;
-  DevBuf<uint32_t> table;
-  uint32_t table_n = 0;
-  // slots, each served by one dispatcher thread taking tasks from this device's queue
-  std::mutex q_mu;
-  std::condition_variable q_cv;
-  std::deque<Task> queue;
-  bool stop = false;
-  std::vector<Slot*> slots;
-  std::vector<std::thread> workers;
-  int runs_inflight = 0;  // under q_mu: runs taken by a slot whose batch pass has not completed
-  std::atomic<uint32_t> run_seq{0};  // run counter: the stream pair of a run (BLSGPU_STREAM_PAIRS)
-  std::atomic<int64_t> load{0};  // cost (sets + pubkeys / 256, x256) of the shards queued or running here (routing)
-  // Urgent lane (BLSGPU_JOB_URGENT, the reference's verifyOnMainThread): one slot with its own dispatcher and two stream
-  // pairs, taking urgent calls from uqueue (under q_mu) one at a time.  It never counts in runs_inflight and never takes
-  // enq_mu, so an urgent call waits for no throughput run on the host; on the device its streams either run on a
-  // reserved CU partition that the pipeline streams are masked off ("urgent_cus" > 0) or at the highest priority.
-  hipStream_t ust[4] = {};         // the urgent lane's streams, created by its dispatcher before its first run
-  std::vector<uint32_t> umask;      // their CU mask (empty: plain streams of priority uprio)
-  int uprio = 0;
-  std::deque<Task> uqueue;
-  Slot* uslot = nullptr;
-  std::thread uworker;
-  std::atomic<int> upending{0};  // urgent calls queued or running here (routing of urgent calls)
-  // batch groups whose equation failed although every job of theirs verified on its own in the fallback -- zero unless a
-  // kernel computed a group's equation wrong (read-only option "spurious_groups"; each one is also logged)
-  std::atomic<uint64_t> spurious_groups{0};
-  int urgent_cus = 0;            // CUs of the partition the streams were created with (0 = none)
-  std::vector<uint32_t> main_mask;  // CU mask of the pipeline and fallback streams (empty = all CUs, priorities)
-  bool blocking_sync = true;        // the dispatchers' wait events block instead of spinning (create_slot_events)
-  std::mutex fail_mu;
-  double fail_rate = 0;  // EWMA over this device's runs of the fraction of invalid sets (group_adapt)
-};
 
 // Device-failure injection (blsgpu_debug_inject, tests only): the next `count` pipeline runs after `skip` more fail as
 // if a HIP call had failed once their batch pass completed.
 std::atomic<int64_t> g_fail_run_skip{0}, g_fail_run_count{0};
 // set on the runtime's dispatcher threads (a "slots" change from a done callback would join its own thread)
 thread_local bool tl_dispatcher = false;
-
-struct Options {  // snapshot taken at the start of each call
-  int64_t group_sets = 1024;
-  int64_t max_devices = 64;
-  bool profile = false;
-  bool dedupe = true;
-  int64_t miller_k = 0;  // pairings per Miller accumulator (shared squarings); 0 = by run size (miller_k_auto)
-  int64_t merge_sets = 131072;  // queued calls a slot merges into one pipeline run (sets), 0 = never
-  int64_t merge_wait_us = 2000;  // while runs are in flight, a slot waits this long for more calls to merge
-  int64_t idle_wait_us = 0;  // on an idle device, a slot waits up to this long while calls keep arriving (bursts)
-  int64_t pipeline_depth = 3;    // runs a device has in flight (taken by a slot, batch pass not yet complete)
-  int64_t group_policy = 0;    // 0 = groups of >= group_sets sets; 1 = the reference pool's jobs / requests / chunks
-  bool serial = false;  // diagnostics: every branch of a run on one stream (each kernel alone on the chip)
-  int64_t miller_lanes = 0;  // lanes per pairing of the one-item-chunk Miller accumulation: 0 = by run size, 1, 2
-  int64_t f_run_max = 16;    // merged runs: longest lane-serial run of the F product tree before the cooperative pairs
-  int64_t lane_tail_min = 0;  // runs of >= this many sets take the lane forms of the Horner passes and the groups'
-                                  // MillerLoop(-g1, S) (0 = never)
-  int64_t lane_tail_parts = 3;    // bit 0: Horner passes, bit 1: MillerLoop(-g1, S)
-  int64_t msm_slice_mid = 32;     // MSM slice length of runs of 1k-32k sets
-  int64_t lines_lanes = 2;        // lanes per message of the Miller lines (1, or 2 = lane pairs: fp2x.hpp)
-  int64_t merge_balance = 0;      // a backlog above merge_sets is cut into equal runs
-  int64_t early_release = 0;      // a run leaves the pipeline count when its message branch is done
-  int64_t tail_on_msg = 0;        // the group stage runs on the pair's high-priority message stream
-  int64_t copy_stream = 0;        // a run's input copy on the table stream (not behind the pair's previous tail)
-  int64_t msm_tree = 1;           // those runs sum each range's slices by a pairwise tree
-  int64_t coop_max = 512;         // runs of <= this many pairings take the cooperative Miller loops (k_miller_coop)
-  int64_t coop_g2_max = 4096;     // runs of <= this many sets take the cooperative [|z|] chains (clearing, subgroup)
-  int64_t coop_excl_max = 512;    // cooperative workgroups take a CU each only in runs of <= this many items
-  int64_t rsig_spec = 1;          // small idle runs form every r_i sig_i beside the batch pass (for the fallback)
-  int64_t spec_large = 1;         // runs above small_max on an idle device take the speculative MSM too
-  int64_t spec_gsm = 0;           // a speculative run's MillerLoop(-g1, S) follows its MSM on the other pair's stream
-  int64_t fb_lane_min = 256;      // fallback check launches of >= this many checks take one lane per check (0 = never)
-  int64_t route_split_sets = 16384;  // a call is split over min(devices, sets / this) devices, else routed whole
-  int64_t acc6_max = 16384;       // one-item-chunk runs of <= this many chunks take the six-lane accumulation
-  int64_t miller_pairs = 0;       // larger runs: the lane-pair accumulation (k_miller_accx, two waves per SIMD)
-  int64_t small_max = 4096;       // runs of <= this many sets are latency-first (speculation, cooperative fallback checks)
-  int64_t fb_direct_min = 1024;   // large runs under load with >= this many retried jobs check each directly (0 = never)
-  int64_t fb_check6 = 2;          // those runs' lane checks: 0 one lane per check; 1 MillerLoop(-g1, S) one lane and the
-                                  // final exponentiation six lanes per check (gt6.hpp); 2 both on six lanes
-  int64_t keep_f = 1;             // the fallback reuses the batch pass's per-set Miller values (0: re-runs the loops)
-  int64_t keep_copy = 0;          // how they are copied aside: 0 hipMemcpyAsync, 1 a copy kernel on the same stream
-  int64_t fb_force_busy = 0;      // tests: every run's fallback takes the under-load forms
-  int64_t urgent_lane = 1;        // calls with a BLSGPU_JOB_URGENT job run on the device's urgent lane
-  int64_t urgent_max_sets = 512;  // larger urgent calls go to the head of the device queue instead
-  int64_t urgent_excl = 0;        // urgent runs may use the exclusive-CU padding of the cooperative kernels
-  int64_t urgent_wait_us = 300;   // the urgent dispatcher lingers this long for more urgent calls of a burst
-  int64_t group_adapt = 1;        // batch groups shrink below group_sets while the device sees invalid sets (DESIGN
-                                  // §5.2: safe once outgrown buffers stay allocated, DevBuf::ensure)
-  bool same_run(const struct Options& o) const {
-    return group_sets == o.group_sets && profile == o.profile && dedupe == o.dedupe && miller_k == o.miller_k &&
-           group_policy == o.group_policy && serial == o.serial && miller_lanes == o.miller_lanes &&
-           f_run_max == o.f_run_max && lane_tail_min == o.lane_tail_min &&
-           lane_tail_parts == o.lane_tail_parts &&
-           msm_slice_mid == o.msm_slice_mid && msm_tree == o.msm_tree &&
-           lines_lanes == o.lines_lanes && merge_balance == o.merge_balance && early_release == o.early_release && tail_on_msg == o.tail_on_msg && copy_stream == o.copy_stream && coop_max == o.coop_max &&
-           coop_g2_max == o.coop_g2_max && coop_excl_max == o.coop_excl_max && rsig_spec == o.rsig_spec && spec_large == o.spec_large && spec_gsm == o.spec_gsm &&
-           fb_lane_min == o.fb_lane_min && acc6_max == o.acc6_max && miller_pairs == o.miller_pairs && small_max == o.small_max &&
-           fb_direct_min == o.fb_direct_min && fb_check6 == o.fb_check6 && fb_force_busy == o.fb_force_busy &&
-           group_adapt == o.group_adapt && keep_f == o.keep_f && keep_copy == o.keep_copy;
-  }
-};
 
 // chunkifyMaximizeChunkSize (reference multithread/utils.ts:4-19): floor(len / min) chunks of ceil(len / count)
 // items, or one chunk when that count is <= 1.  Returns the items per chunk.
@@ -428,6 +106,10 @@ inline void add_slices(std::vector<uint32_t>& slices, std::vector<uint32_t>& ran
   range_slices.push_back((uint32_t)(slices.size() / 2));
 }
 
+}  // namespace
+
+namespace blsgpu_rt __attribute__((visibility("hidden"))) {  // (Task, in runtime_internal.hpp, points to a Call)
+
 struct Shard {
   uint32_t job_begin, job_end;  // job range
   uint32_t set_begin, set_end;  // set range
@@ -466,29 +148,7 @@ struct Call {
   int status = BLSGPU_OK;
 };
 
-}  // namespace
-
-struct blsgpu_ctx {
-  std::vector<Device*> devs;
-  std::atomic<bool> closed{false};
-  std::mutex active_mu;  // calls in progress (sync and async): destroy waits for zero
-  std::condition_variable active_cv;
-  int active = 0;
-  std::mutex table_mu;  // serializes uploads
-  std::mutex opt_mu;
-  Options opt;
-  int64_t slots_per_device = 2;  // set at init from the hardware queues (default_slots)
-  int64_t hw_queues = 4;
-  std::mutex slots_mu;  // slot creation / resizing
-  bool slots_started = false;
-  std::atomic<uint32_t> route_seq{0};  // rotating tie-break of route_rule
-  // urgent lane partition (set before the first call: the streams are created with it): CUs per device reserved for
-  // the urgent streams, a multiple of 8; with urgent_isolate the pipeline streams are masked off them
-  int64_t urgent_cus = 0;
-  int64_t urgent_isolate = 1;  // (no effect without a partition)
-  int64_t blocking_sync = 1;   // dispatchers block on their runs' completion events instead of spinning
-  int64_t pipeline_prio = 1;   // the pipeline's message and tail streams take the device's highest priority
-};
+}  // namespace blsgpu_rt
 
 namespace {
 
@@ -542,43 +202,6 @@ uint32_t route_rule(uint32_t n_sets, uint32_t n_dev, const int64_t* load, int64_
   return k;
 }
 
-// ---- message deduplication: open addressing on the 32-byte signing roots ----------------------------------
-struct MsgIndex {
-  std::vector<uint32_t> slot;  // 1 + unique index, 0 = empty
-  uint64_t key;
-  explicit MsgIndex(uint32_t n, uint64_t k) : key(k) {
-    size_t cap = 16;
-    while (cap < (size_t)n * 2) cap <<= 1;
-    slot.assign(cap, 0);
-  }
-  static uint64_t mix(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-  }
-  size_t hash(const uint8_t* msgs, uint32_t i) const {
-    uint64_t w[4];
-    memcpy(w, msgs + (size_t)i * 32, 32);
-    return (size_t)(mix(w[0] ^ key) ^ mix(w[1] + key) ^ w[2] ^ (w[3] << 1)) & (slot.size() - 1);
-  }
-  // returns the unique index of msg; appends to `uniq` (set indices of first occurrences) when new
-  uint32_t find_or_add(const uint8_t* msgs, uint32_t i, std::vector<uint32_t>& uniq) {
-    return find_or_add_h(msgs, i, hash(msgs, i), uniq);
-  }
-  uint32_t find_or_add_h(const uint8_t* msgs, uint32_t i, size_t h, std::vector<uint32_t>& uniq) {
-    const size_t mask = slot.size() - 1;
-    for (;;) {
-      const uint32_t s = slot[h];
-      if (!s) {
-        uniq.push_back(i);
-        slot[h] = (uint32_t)uniq.size();
-        return (uint32_t)uniq.size() - 1;
-      }
-      if (memcmp(msgs + (size_t)uniq[s - 1] * 32, msgs + (size_t)i * 32, 32) == 0) return s - 1;
-      h = (h + 1) & mask;
-    }
-  }
-};
 
 // Batch-group size for a run (group_adapt).  A group costs a fixed ~14.7k Montgomery multiplications (its
 // MillerLoop(-g1, S) 5,747, final exponentiation 7,835, MSM range 1,085; lodestar_amd/op_counts.json), and when it fails
@@ -620,9 +243,6 @@ static bool host_trace() {
     return v && v[0] == '1';
   }();
   return on;
-}
-static double ms_since(std::chrono::steady_clock::time_point t) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
 thread_local std::chrono::steady_clock::time_point tl_run_t0;
 thread_local double tl_merge_ms = 0;
@@ -1563,19 +1183,6 @@ int validate_batch(const blsgpu_batch* b) {
   return BLSGPU_OK;
 }
 
-bool enter(blsgpu_ctx* ctx) {  // register a call in progress unless the context is closing
-  std::lock_guard<std::mutex> lk(ctx->active_mu);
-  if (ctx->closed) return false;
-  ctx->active++;
-  return true;
-}
-void leave(blsgpu_ctx* ctx) {
-  {
-    std::lock_guard<std::mutex> lk(ctx->active_mu);
-    ctx->active--;
-  }
-  ctx->active_cv.notify_all();
-}
 
 void finish_call(Call* c) {
   blsgpu_stats local{};
@@ -2461,9 +2068,8 @@ void launch_call(blsgpu_ctx* ctx, Call* c) {
   }
 }
 
-// The call's scalar key and message-index hash key from its seed (batch_rand.hpp): seed 0 = 256 bits of OS
-// entropy, else the comparison-run key of the seed.  false = no entropy: the call must fail (never a constant).
-bool resolve_key(uint64_t seed, batch_rand::Key& key, uint64_t& hash_key) {
+}  // namespace
+bool blsgpu_rt::resolve_key(uint64_t seed, batch_rand::Key& key, uint64_t& hash_key) {
   if (seed == 0) {
     if (!batch_rand::os_key(key)) return false;
     hash_key = batch_rand::hash_key(key);  // its own keystream block, not key material
@@ -2473,6 +2079,7 @@ bool resolve_key(uint64_t seed, batch_rand::Key& key, uint64_t& hash_key) {
   }
   return true;
 }
+namespace {
 
 void reject_all(const blsgpu_batch* b, int8_t* job_result, int code) {
   if (job_result)
@@ -3045,667 +2652,6 @@ const char* blsgpu_code_name(int code) {
     case BLSGPU_ERR_ENTROPY: return "BLSGPU_ERR_ENTROPY";
     default: return nullptr;
   }
-}
-
-// ---- synchronous helpers on device 0's helper stream ----------------------------------------------------------
-int blsgpu_aggregate_pubkeys(blsgpu_ctx* ctx, const blsgpu_batch* b, uint8_t* out, uint32_t out_len,
-                             int8_t* status) {
-  if (!ctx || ctx->devs.empty() || !b || !out || !status || (out_len != 48 && out_len != 96)) return BLSGPU_ERR_ARGS;
-  const uint32_t n = b->n_sets;
-  if (n == 0) return BLSGPU_OK;
-  if (!b->pk_bytes && (!b->set_pk_first || !b->pk_index)) return BLSGPU_ERR_ARGS;
-  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
-  Device* d = ctx->devs[0];
-  int rc = BLSGPU_OK;
-  try {
-    std::lock_guard<std::mutex> hl(d->helper_mu);
-    std::shared_lock<std::shared_mutex> tl(d->table_mu);
-    HIPCHK(hipSetDevice(d->id));
-    // set_pk_first (a synthetic 1-key-per-set layout in single-key bytes mode) | keys | out | status
-    std::vector<uint32_t> spf(n + 1);
-    for (uint32_t i = 0; i <= n; i++) spf[i] = b->set_pk_first ? b->set_pk_first[i] : i;
-    const uint32_t npk = spf[n];
-    if (!b->pk_bytes) {
-      for (uint32_t k = 0; k < npk; k++)
-        if (b->pk_index[k] >= d->table_n) rc = BLSGPU_ERR_ARGS;
-    }
-    if (rc == BLSGPU_OK) {
-      const size_t key_bytes = b->pk_bytes ? (size_t)npk * 96 : (size_t)npk * 4;
-      const size_t o_keys = al256((size_t)(n + 1) * 4), o_out = al256(o_keys + key_bytes),
-                   o_st = al256(o_out + (size_t)n * out_len), total = o_st + 3 * (size_t)n;
-      Slot& sl = d->helper;
-      sl.d_in.ensure(total);
-      sl.d_work.ensure((size_t)n * W_G1J);
-      hipStream_t s = d->table_stream;
-      uint8_t* din = sl.d_in.p;
-      HIPCHK(hipMemcpyAsync(din, spf.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + o_keys, b->pk_bytes ? (const void*)b->pk_bytes : (const void*)b->pk_index,
-                            key_bytes, hipMemcpyHostToDevice, s));
-      PipelineBuffers pb;
-      memset(&pb, 0, sizeof pb);
-      pb.n = n;
-      pb.set_pk_first = reinterpret_cast<uint32_t*>(din);
-      pb.pk_bytes = b->pk_bytes ? din + o_keys : nullptr;
-      pb.pk_index = b->pk_bytes ? nullptr : reinterpret_cast<uint32_t*>(din + o_keys);
-      pb.pk_table = d->table.p;
-      pb.pk_table_n = d->table_n;
-      pb.pk_jac = sl.d_work.p;
-      pb.status = reinterpret_cast<int8_t*>(din + o_st);
-      launch_pk_aggregate(pb, n, s);
-      launch_pk_serialize(pb, n, din + o_out, out_len, s);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(out, din + o_out, (size_t)n * out_len, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(status, din + o_st, n, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-    }
-  } catch (HipError&) {
-    rc = BLSGPU_DEVICE_ERROR;
-  }
-  leave(ctx);
-  return rc;
-}
-
-int blsgpu_aggregate_signatures(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
-                                const uint8_t* sigs, uint32_t sig_stride, const uint32_t* sig_len, uint32_t flags,
-                                uint8_t* out, uint32_t out_len, int8_t* status, uint32_t* first_bad) {
-  if (!ctx || ctx->devs.empty() || !group_first || !sigs || !sig_len || !out || !status) return BLSGPU_ERR_ARGS;
-  if ((out_len != 96 && out_len != 192) || sig_stride < 96 || (flags & ~BLSGPU_AGG_VALIDATE)) return BLSGPU_ERR_ARGS;
-  if (n_groups == 0) return BLSGPU_OK;
-  if (group_first[0] != 0) return BLSGPU_ERR_ARGS;
-  for (uint32_t g = 0; g < n_groups; g++)
-    if (group_first[g + 1] < group_first[g]) return BLSGPU_ERR_ARGS;
-  const uint32_t n = group_first[n_groups], G = n_groups;
-  if (n > (1u << 20)) return BLSGPU_ERR_ARGS;
-  if (sig_stride < 192)
-    for (uint32_t k = 0; k < n; k++)
-      if (sig_len[k] == 192) return BLSGPU_ERR_ARGS;
-  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
-  Device* d = ctx->devs[0];
-  int rc = BLSGPU_OK;
-  try {
-    std::lock_guard<std::mutex> hl(d->helper_mu);
-    HIPCHK(hipSetDevice(d->id));
-    // group_first | sig_len | sigs | out | first_bad | group status | signature status | signature flags
-    const size_t o_len = al256((size_t)(G + 1) * 4), o_sigs = al256(o_len + (size_t)n * 4),
-                 o_out = al256(o_sigs + (size_t)n * sig_stride), o_fb = al256(o_out + (size_t)G * out_len),
-                 o_gst = al256(o_fb + (size_t)G * 4), o_st = al256(o_gst + G), o_fl = al256(o_st + n),
-                 total = o_fl + n;
-    Slot& sl = d->helper;
-    sl.d_in.ensure(total);
-    sl.d_work.ensure((size_t)n * W_G2A + (size_t)G * W_G2J);
-    hipStream_t s = d->table_stream;
-    uint8_t* din = sl.d_in.p;
-    HIPCHK(hipMemcpyAsync(din, group_first, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
-    if (n) {
-      HIPCHK(hipMemcpyAsync(din + o_len, sig_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + o_sigs, sigs, (size_t)n * sig_stride, hipMemcpyHostToDevice, s));
-    }
-    PipelineBuffers pb;
-    memset(&pb, 0, sizeof pb);
-    pb.n = n;
-    pb.sigs = din + o_sigs;
-    pb.sig_len = reinterpret_cast<uint32_t*>(din + o_len);
-    pb.sig_stride = sig_stride;
-    pb.sig_aff = sl.d_work.p;
-    pb.flags = din + o_fl;
-    pb.status = reinterpret_cast<int8_t*>(din + o_st);
-    const uint32_t* d_first = reinterpret_cast<uint32_t*>(din);
-    uint32_t* agg = sl.d_work.p + (size_t)n * W_G2A;
-    int8_t* d_gst = reinterpret_cast<int8_t*>(din + o_gst);
-    uint32_t* d_fb = reinterpret_cast<uint32_t*>(din + o_fb);
-    // small calls (the pool insert) take the cooperative subgroup check, as small verification runs do
-    launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, (flags & BLSGPU_AGG_VALIDATE) != 0);
-    launch_sig_aggregate(pb, d_first, G, n, agg, d_gst, d_fb, s);
-    launch_sig_agg_serialize(d_first, G, agg, d_gst, din + o_out, out_len, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, din + o_out, (size_t)G * out_len, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(status, din + o_gst, G, hipMemcpyDeviceToHost, s));
-    if (first_bad) HIPCHK(hipMemcpyAsync(first_bad, din + o_fb, (size_t)G * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-  } catch (HipError&) {
-    rc = BLSGPU_DEVICE_ERROR;
-  }
-  leave(ctx);
-  return rc;
-}
-
-uint32_t blsgpu_sig_agg_lanes(uint32_t n_groups, uint32_t n_sigs) { return sig_agg_lanes(n_groups, n_sigs); }
-
-int blsgpu_randomness_words(uint32_t n, uint64_t seed, uint64_t* words) {
-  if (n && !words) return BLSGPU_ERR_ARGS;
-  batch_rand::Key key;
-  uint64_t hash_key = 0;
-  if (!resolve_key(seed, key, hash_key)) return BLSGPU_ERR_ENTROPY;
-  batch_rand::words(key, 0, n, words);
-  return BLSGPU_OK;
-}
-
-int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
-                                     const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
-                                     uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed, uint8_t* out_pk,
-                                     uint32_t out_pk_len, uint8_t* out_sig, uint32_t out_sig_len, int8_t* status,
-                                     uint32_t* first_bad) {
-  if (!ctx || ctx->devs.empty() || !group_first || !sigs || !sig_len || !out_pk || !out_sig || !status)
-    return BLSGPU_ERR_ARGS;
-  if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
-  if ((out_pk_len != 48 && out_pk_len != 96) || (out_sig_len != 96 && out_sig_len != 192) || sig_stride < 96)
-    return BLSGPU_ERR_ARGS;
-  if (n_groups == 0) return BLSGPU_OK;
-  if (group_first[0] != 0) return BLSGPU_ERR_ARGS;
-  for (uint32_t g = 0; g < n_groups; g++)
-    if (group_first[g + 1] < group_first[g]) return BLSGPU_ERR_ARGS;
-  const uint32_t n = group_first[n_groups], G = n_groups;
-  if (n > (1u << 20)) return BLSGPU_ERR_ARGS;
-  if (sig_stride < 192)
-    for (uint32_t k = 0; k < n; k++)
-      if (sig_len[k] == 192) return BLSGPU_ERR_ARGS;
-  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
-  // the call's scalars, before anything is written or reaches the device
-  std::vector<uint64_t> words(n);
-  {
-    batch_rand::Key key;
-    uint64_t hash_key = 0;
-    if (!resolve_key(seed, key, hash_key)) {
-      leave(ctx);
-      return BLSGPU_ERR_ENTROPY;
-    }
-    batch_rand::words(key, 0, n, words.data());
-  }
-  Device* d = ctx->devs[0];
-  int rc = BLSGPU_OK;
-  try {
-    std::lock_guard<std::mutex> hl(d->helper_mu);
-    std::shared_lock<std::shared_mutex> tl(d->table_mu);
-    HIPCHK(hipSetDevice(d->id));
-    if (pk_index)
-      for (uint32_t k = 0; k < n; k++)
-        if (pk_index[k] >= d->table_n) rc = BLSGPU_ERR_ARGS;
-    if (rc == BLSGPU_OK) {
-      const uint32_t L = awr_lanes(G, n), lanes = awr_launch_lanes(G, L);
-      // words | group_first | sig_len | sigs | keys | out_pk | out_sig | first_bad | error indices | group status |
-      // error codes | signature status | signature flags
-      const size_t key_bytes = pk_bytes ? (size_t)n * 96 : (size_t)n * 4;
-      const size_t o_gf = al256((size_t)n * 8), o_len = al256(o_gf + (size_t)(G + 1) * 4),
-                   o_sigs = al256(o_len + (size_t)n * 4), o_keys = al256(o_sigs + (size_t)n * sig_stride),
-                   o_opk = al256(o_keys + key_bytes), o_osig = al256(o_opk + (size_t)G * out_pk_len),
-                   o_fb = al256(o_osig + (size_t)G * out_sig_len), o_ek = al256(o_fb + (size_t)G * 4),
-                   o_gst = al256(o_ek + (size_t)G * 8), o_ec = al256(o_gst + G), o_st = al256(o_ec + 2 * (size_t)G),
-                   o_fl = al256(o_st + n), total = o_fl + n;
-      Slot& sl = d->helper;
-      sl.d_in.ensure(total);
-      sl.d_work.ensure((size_t)n * W_G2A + (size_t)lanes * AWR_TAB_WORDS + (size_t)G * (W_G1J + W_G2J));
-      hipStream_t s = d->table_stream;
-      uint8_t* din = sl.d_in.p;
-      HIPCHK(hipMemcpyAsync(din + o_gf, group_first, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
-      if (n) {
-        HIPCHK(hipMemcpyAsync(din, words.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(din + o_len, sig_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(din + o_sigs, sigs, (size_t)n * sig_stride, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(din + o_keys, pk_bytes ? (const void*)pk_bytes : (const void*)pk_index, key_bytes,
-                              hipMemcpyHostToDevice, s));
-      }
-      PipelineBuffers pb;
-      memset(&pb, 0, sizeof pb);
-      pb.n = n;
-      pb.sigs = din + o_sigs;
-      pb.sig_len = reinterpret_cast<uint32_t*>(din + o_len);
-      pb.sig_stride = sig_stride;
-      pb.sig_aff = sl.d_work.p;
-      pb.flags = din + o_fl;
-      pb.status = reinterpret_cast<int8_t*>(din + o_st);
-      AwrBuffers ab;
-      memset(&ab, 0, sizeof ab);
-      ab.n = n;
-      ab.n_groups = G;
-      ab.group_first = reinterpret_cast<uint32_t*>(din + o_gf);
-      ab.words = reinterpret_cast<uint64_t*>(din);
-      ab.pk_bytes = pk_bytes ? din + o_keys : nullptr;
-      ab.pk_index = pk_bytes ? nullptr : reinterpret_cast<uint32_t*>(din + o_keys);
-      ab.pk_table = d->table.p;
-      ab.pk_table_n = d->table_n;
-      ab.sig_aff = pb.sig_aff;
-      ab.sig_flags = pb.flags;
-      ab.sig_status = pb.status;
-      ab.tab = sl.d_work.p + (size_t)n * W_G2A;
-      ab.tab_n = lanes;
-      ab.sum_pk = ab.tab + (size_t)lanes * AWR_TAB_WORDS;
-      ab.sum_sig = ab.sum_pk + (size_t)G * W_G1J;
-      ab.err_k = reinterpret_cast<uint32_t*>(din + o_ek);
-      ab.err_c = reinterpret_cast<int8_t*>(din + o_ec);
-      int8_t* d_gst = reinterpret_cast<int8_t*>(din + o_gst);
-      uint32_t* d_fb = reinterpret_cast<uint32_t*>(din + o_fb);
-      // small calls take the cooperative subgroup check, as small verification runs do
-      launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, true);
-      launch_awr_sums(ab, L, s);
-      launch_awr_serialize(ab, din + o_opk, out_pk_len, din + o_osig, out_sig_len, d_gst, d_fb, s);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(out_pk, din + o_opk, (size_t)G * out_pk_len, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(out_sig, din + o_osig, (size_t)G * out_sig_len, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(status, din + o_gst, G, hipMemcpyDeviceToHost, s));
-      if (first_bad) HIPCHK(hipMemcpyAsync(first_bad, din + o_fb, (size_t)G * 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-    }
-  } catch (HipError&) {
-    rc = BLSGPU_DEVICE_ERROR;
-  }
-  leave(ctx);
-  return rc;
-}
-
-uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets) { return awr_lanes(n_groups, n_sets); }
-
-// ---- one-call same-message verification ------------------------------------------------------------------------
-// A phase of at most kSameCoopMax pairings takes the cooperative kernels (a workgroup per Miller loop and per check:
-// latency), a larger one the lane forms (throughput).  512 is option "coop_max"'s default, taken as a constant: the
-// helper calls read no option.
-constexpr uint32_t kSameCoopMax = 512;
-uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags) {
-  return (flags & BLSGPU_SAME_LANE_FORMS) || n_items > kSameCoopMax ? 1u : 0u;
-}
-namespace {
-// diagnostics (tools/bench_same_message.py): the three branches of the group phase on one stream
-inline bool same_serial() {
-  static const bool on = [] {
-    const char* v = getenv("BLSGPU_SAME_SERIAL");
-    return v && v[0] == '1';
-  }();
-  return on;
-}
-// Miller values and checks of one phase: item i < n_items pairs pk_aff[i] (W_G1A, stride n_items) with H(msg_idx[i]) when
-// include[i], and ok[i] = FinalExp(F_i * MillerLoop(-g1, S_i)) == 1 with S (W_G2J, stride n_items).  iota = 0, 1, ..,
-// n_items: one item per Miller chunk.  Cooperative form: k_miller_coop and k_group_check with its own Miller loop.
-// Lane form: the messages' stored lines (pm.lines), k_miller_acc6 (six lanes per pairing), MillerLoop(-g1, S) on one
-// lane per item and the final exponentiation on six (k_group_check6).
-void same_pairing_phase(const PipelineBuffers& pm, uint32_t n_items, const uint32_t* iota, uint32_t* pk_aff,
-                        uint8_t* include, const uint32_t* msg_idx, const uint32_t* S, uint32_t* F, uint32_t* Gs,
-                        uint8_t* ok, bool lane, hipStream_t s) {
-  PipelineBuffers pb = pm;
-  pb.n = n_items;
-  pb.pk_aff = pk_aff;
-  pb.include = include;
-  pb.msg_idx = msg_idx;
-  pb.n_chunks = n_items;
-  pb.chunk_first = iota;
-  pb.chunk_items = iota;
-  pb.f_chunk = F;
-  if (!lane) {
-    launch_miller_coop(pb, false, s, false);
-    launch_group_check(S, F, n_items, ok, s);
-  } else {
-    launch_miller_acc6(pb, false, s);
-    launch_group_sig_miller(S, n_items, Gs, s, false, true);
-    launch_group_check6(F, Gs, n_items, ok, s);
-  }
-}
-}  // namespace
-
-int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first, const uint8_t* msgs,
-                               const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
-                               uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed, uint32_t flags,
-                               int8_t* set_result, int8_t* group_result, blsgpu_same_message_stats* stats) {
-  if (!ctx || ctx->devs.empty() || !group_first || !msgs || !sigs || !sig_len || !set_result) return BLSGPU_ERR_ARGS;
-  if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
-  if (sig_stride < 96 || (flags & ~BLSGPU_SAME_LANE_FORMS)) return BLSGPU_ERR_ARGS;
-  if (n_groups == 0) {
-    if (stats) memset(stats, 0, sizeof *stats);
-    return BLSGPU_OK;
-  }
-  if (group_first[0] != 0) return BLSGPU_ERR_ARGS;
-  for (uint32_t g = 0; g < n_groups; g++)
-    if (group_first[g + 1] < group_first[g]) return BLSGPU_ERR_ARGS;
-  const uint32_t n = group_first[n_groups], G = n_groups;
-  if (n > (1u << 20)) return BLSGPU_ERR_ARGS;
-  if (sig_stride < 192)
-    for (uint32_t k = 0; k < n; k++)
-      if (sig_len[k] == 192) return BLSGPU_ERR_ARGS;
-  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
-  // the call's scalars, before anything is written or reaches the device
-  std::vector<uint64_t> words(n);
-  uint64_t hash_key = 0;
-  {
-    batch_rand::Key key;
-    if (!resolve_key(seed, key, hash_key)) {
-      leave(ctx);
-      return BLSGPU_ERR_ENTROPY;
-    }
-    batch_rand::words(key, 0, n, words.data());
-  }
-  // messages, deduplicated as run_shard does: group g signs unique message gmsg[g]
-  std::vector<uint32_t> gmsg(G), uniq;
-  {
-    MsgIndex mi(G, hash_key ^ 0x6a09e667f3bcc908ull);
-    for (uint32_t g = 0; g < G; g++) gmsg[g] = mi.find_or_add(msgs, g, uniq);
-  }
-  const uint32_t U = (uint32_t)uniq.size();
-  Device* d = ctx->devs[0];
-  int rc = BLSGPU_OK;
-  std::vector<int8_t> h_set(n), h_grp(G);
-  blsgpu_same_message_stats st;
-  memset(&st, 0, sizeof st);
-  st.unique_messages = U;
-  bool streams_used = false;
-  try {
-    std::lock_guard<std::mutex> hl(d->helper_mu);
-    std::shared_lock<std::shared_mutex> tl(d->table_mu);
-    HIPCHK(hipSetDevice(d->id));
-    if (pk_index)
-      for (uint32_t k = 0; k < n; k++)
-        if (pk_index[k] >= d->table_n) rc = BLSGPU_ERR_ARGS;
-    if (rc == BLSGPU_OK) {
-      if (!d->same_st[0]) {
-        for (auto& e : d->same_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIPCHK(hipStreamCreateWithFlags(&d->same_st[1], hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&d->same_st[0], hipStreamNonBlocking));
-      }
-      const auto t0 = std::chrono::steady_clock::now();
-      const bool serial = same_serial();
-      hipStream_t s = d->table_stream, sb = serial ? s : d->same_st[0], sc = serial ? s : d->same_st[1];
-      const bool lane_g = blsgpu_same_message_form(G, flags) != 0;
-      const uint32_t L = awr_lanes(G, n), lanes = awr_launch_lanes(G, L);
-      // input arena: words | group_first | sig_len | sigs | keys | unique messages | group message indices | iota
-      const size_t key_bytes = pk_bytes ? (size_t)n * 96 : (size_t)n * 4;
-      const size_t o_gf = al256((size_t)n * 8), o_len = al256(o_gf + (size_t)(G + 1) * 4),
-                   o_sigs = al256(o_len + (size_t)n * 4), o_keys = al256(o_sigs + (size_t)n * sig_stride),
-                   o_umsg = al256(o_keys + key_bytes), o_gmsg = al256(o_umsg + (size_t)U * 32),
-                   o_iota = al256(o_gmsg + (size_t)G * 4), in_total = al256(o_iota + (size_t)(G + 1) * 4);
-      // byte arrays: error indices | error codes | signature status | signature flags | message flags | group include |
-      // group code | group verdict | group_result | set_result
-      const size_t b_ek = 0, b_ec = al256(b_ek + (size_t)G * 8), b_st = al256(b_ec + 2 * (size_t)G),
-                   b_fl = al256(b_st + n), b_mf = al256(b_fl + n), b_inc = al256(b_mf + U), b_code = al256(b_inc + G),
-                   b_ok = al256(b_code + G), b_gres = al256(b_ok + G), b_sres = al256(b_gres + G),
-                   bytes_total = al256(b_sres + n);
-      Slot& sl = d->helper;
-      // every buffer of the group phase grows here, while none of the three streams has work (each call ends with all
-      // of them synchronized); the retry phase grows only buffers the group phase does not use, after its synchronize
-      sl.d_in.ensure(in_total);
-      sl.d_bytes.ensure(bytes_total);
-      // work: sig_aff | window scratch of the G2 sum | of the G1 sum | sum_pk | sum_sig | pk_aff | 1 / z | F | G |
-      // message branch (inv, h_aff, h_jac, h_norm, h_prep, h_q)
-      const size_t nm = U;
-      sl.d_work.ensure((size_t)n * W_G2A + 2 * (size_t)lanes * AWR_TAB_WORDS +
-                       (size_t)G * (W_G1J + W_G2J + W_G1A + W_FP + 2 * W_FP12) +
-                       nm * (W_FP + W_G2A + W_G2J + W_FP + 14 * W_FP + 2 * W_G2J));
-      if (lane_g) sl.d_lines.ensure(nm * kMillerLineWords);
-      streams_used = true;
-      uint8_t* din = sl.d_in.p;
-      uint8_t* db = sl.d_bytes.p;
-      std::vector<uint32_t> iota((size_t)G + 1);
-      for (uint32_t g = 0; g <= G; g++) iota[g] = g;
-      std::vector<uint8_t> umsgs((size_t)U * 32);
-      for (uint32_t u = 0; u < U; u++) memcpy(umsgs.data() + (size_t)u * 32, msgs + (size_t)uniq[u] * 32, 32);
-      HIPCHK(hipMemcpyAsync(din + o_gf, group_first, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + o_umsg, umsgs.data(), (size_t)U * 32, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + o_gmsg, gmsg.data(), (size_t)G * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + o_iota, iota.data(), (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
-      if (n) {
-        HIPCHK(hipMemcpyAsync(din, words.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(din + o_len, sig_len, (size_t)n * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(din + o_sigs, sigs, (size_t)n * sig_stride, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(din + o_keys, pk_bytes ? (const void*)pk_bytes : (const void*)pk_index, key_bytes,
-                              hipMemcpyHostToDevice, s));
-      }
-      PipelineBuffers pb;  // the signature decode
-      memset(&pb, 0, sizeof pb);
-      pb.n = n;
-      pb.sigs = din + o_sigs;
-      pb.sig_len = reinterpret_cast<uint32_t*>(din + o_len);
-      pb.sig_stride = sig_stride;
-      pb.flags = db + b_fl;
-      pb.status = reinterpret_cast<int8_t*>(db + b_st);
-      uint32_t* w = sl.d_work.p;
-      pb.sig_aff = w; w += (size_t)n * W_G2A;
-      AwrBuffers ab;
-      memset(&ab, 0, sizeof ab);
-      ab.n = n;
-      ab.n_groups = G;
-      ab.group_first = reinterpret_cast<uint32_t*>(din + o_gf);
-      ab.words = reinterpret_cast<uint64_t*>(din);
-      ab.pk_bytes = pk_bytes ? din + o_keys : nullptr;
-      ab.pk_index = pk_bytes ? nullptr : reinterpret_cast<uint32_t*>(din + o_keys);
-      ab.pk_table = d->table.p;
-      ab.pk_table_n = d->table_n;
-      ab.sig_aff = pb.sig_aff;
-      ab.sig_flags = pb.flags;
-      ab.sig_status = pb.status;
-      ab.tab = w; w += (size_t)lanes * AWR_TAB_WORDS;
-      ab.tab_n = lanes;
-      AwrBuffers ab_pk = ab;  // the G1 sum runs beside the G2 sum: its own window scratch
-      ab_pk.tab = w; w += (size_t)lanes * AWR_TAB_WORDS;
-      ab.sum_pk = ab_pk.sum_pk = w; w += (size_t)G * W_G1J;
-      ab.sum_sig = ab_pk.sum_sig = w; w += (size_t)G * W_G2J;
-      ab.err_k = ab_pk.err_k = reinterpret_cast<uint32_t*>(db + b_ek);
-      ab.err_c = ab_pk.err_c = reinterpret_cast<int8_t*>(db + b_ec);
-      uint32_t* g_pk_aff = w; w += (size_t)G * W_G1A;
-      uint32_t* g_inv = w; w += (size_t)G * W_FP;
-      uint32_t* g_F = w; w += (size_t)G * W_FP12;
-      uint32_t* g_G = w; w += (size_t)G * W_FP12;
-      PipelineBuffers pm;  // the message branch
-      memset(&pm, 0, sizeof pm);
-      pm.umsgs = din + o_umsg;
-      pm.n_umsg = U;
-      pm.nm = (uint32_t)nm;
-      pm.inv_buf = w; w += nm * W_FP;
-      pm.h_aff = w; w += nm * W_G2A;
-      pm.h_jac = w; w += nm * W_G2J;
-      pm.h_norm = w; w += nm * W_FP;
-      pm.h_prep = w; w += nm * 14 * W_FP;
-      pm.h_q = w;
-      pm.mflags = db + b_mf;
-      pm.lines = sl.d_lines.p;
-      uint8_t* g_inc = db + b_inc;
-      int8_t* g_code = reinterpret_cast<int8_t*>(db + b_code);
-      uint8_t* g_ok = db + b_ok;
-      int8_t* d_gres = reinterpret_cast<int8_t*>(db + b_gres);
-      int8_t* d_sres = reinterpret_cast<int8_t*>(db + b_sres);
-      const uint32_t* d_gmsg = reinterpret_cast<uint32_t*>(din + o_gmsg);
-      const uint32_t* d_iota = reinterpret_cast<uint32_t*>(din + o_iota);
-      // ---- group phase: three branches from the input copy, joined into s
-      HIPCHK(hipEventRecord(d->same_ev[0], s));
-      if (!serial) {
-        HIPCHK(hipStreamWaitEvent(sb, d->same_ev[0], 0));
-        HIPCHK(hipStreamWaitEvent(sc, d->same_ev[0], 0));
-      }
-      // (a) signatures: decode + subgroup check (cooperative for small calls, as small verification runs), S_g
-      launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, true);
-      launch_awr_sum_sig(ab, L, s);
-      // (b) keys: P_g and the batch inverses of its z
-      launch_awr_sum_pk(ab_pk, L, sb);
-      launch_batch_inv(ab.sum_pk, G, 2 * W_FP, g_inv, G, sb);
-      HIPCHK(hipEventRecord(d->same_ev[1], sb));
-      // (c) messages: H(m) affine, and in the lane form its Miller lines
-      bool have_lines = false;
-      launch_hash_to_g2(pm, sc, U <= 4096, false);
-      launch_h_affine(pm, sc);
-      if (lane_g) {
-        launch_miller_lines2(pm, sc);
-        have_lines = true;
-      }
-      HIPCHK(hipEventRecord(d->same_ev[2], sc));
-      if (!serial) {
-        HIPCHK(hipStreamWaitEvent(s, d->same_ev[1], 0));
-        HIPCHK(hipStreamWaitEvent(s, d->same_ev[2], 0));
-      }
-      launch_same_group_items(ab, g_inv, g_pk_aff, g_inc, g_code, s);
-      same_pairing_phase(pm, G, d_iota, g_pk_aff, g_inc, d_gmsg, ab.sum_sig, g_F, g_G, g_ok, lane_g, s);
-      launch_same_group_results(ab.group_first, G, n, g_inc, g_code, g_ok, d_sres, d_gres, s);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(h_grp.data(), d_gres, G, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
-      if (lane_g) st.form |= 1;
-      // ---- retry phase: every set of a non-empty group whose check did not hold, on its own with r = 1
-      std::vector<uint32_t> rlist, rmsg, riota;  // (alive until the final synchronize: they are copied from)
-      for (uint32_t g = 0; g < G; g++) {
-        if (group_first[g + 1] == group_first[g]) continue;
-        if (h_grp[g] == 1) {
-          st.groups_accepted++;
-          continue;
-        }
-        st.groups_retried++;
-        for (uint32_t k = group_first[g]; k < group_first[g + 1]; k++) {
-          rlist.push_back(k);
-          rmsg.push_back(gmsg[g]);
-        }
-      }
-      const uint32_t nr = (uint32_t)rlist.size();
-      st.retry_sets = nr;
-      if (nr) {
-        const bool lane_r = blsgpu_same_message_form(nr, flags) != 0;
-        // list | message indices | iota ; bytes: include | code | verdict
-        const size_t r_msg = al256((size_t)nr * 4) / 4, r_iota = r_msg + al256((size_t)nr * 4) / 4,
-                     r_total = r_iota + nr + 1;
-        sl.d_list.ensure(r_total);
-        sl.d_ok.ensure(3 * al256(nr));
-        sl.d_fb.ensure((size_t)nr * W_G1A);
-        sl.d_S.ensure((size_t)nr * W_G2J);
-        sl.d_F.ensure((size_t)nr * W_FP12);
-        if (lane_r) sl.d_G.ensure((size_t)nr * W_FP12);
-        if (lane_r && !have_lines) {
-          sl.d_lines.ensure(nm * kMillerLineWords);
-          pm.lines = sl.d_lines.p;
-        }
-        riota.resize((size_t)nr + 1);
-        for (uint32_t q = 0; q <= nr; q++) riota[q] = q;
-        uint32_t* dl = sl.d_list.p;
-        HIPCHK(hipMemcpyAsync(dl, rlist.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dl + r_msg, rmsg.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dl + r_iota, riota.data(), (size_t)(nr + 1) * 4, hipMemcpyHostToDevice, s));
-        uint8_t* r_inc = sl.d_ok.p;
-        int8_t* r_code = reinterpret_cast<int8_t*>(sl.d_ok.p + al256(nr));
-        uint8_t* r_ok = sl.d_ok.p + 2 * al256(nr);
-        launch_same_retry_items(ab, dl, nr, sl.d_fb.p, sl.d_S.p, r_inc, r_code, s);
-        if (lane_r && !have_lines) launch_miller_lines2(pm, s);
-        same_pairing_phase(pm, nr, dl + r_iota, sl.d_fb.p, r_inc, dl + r_msg, sl.d_S.p, sl.d_F.p, sl.d_G.p, r_ok, lane_r,
-                           s);
-        launch_same_retry_results(dl, nr, r_inc, r_code, r_ok, d_sres, s);
-        HIPCHK(hipGetLastError());
-        if (lane_r) st.form |= 2;
-      }
-      if (n) HIPCHK(hipMemcpyAsync(h_set.data(), d_sres, n, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      st.device_ms = ms_since(t0);
-    }
-  } catch (HipError&) {
-    rc = BLSGPU_DEVICE_ERROR;
-    // no branch may outlive the call: the next helper call reuses, and may grow, the buffers they work on
-    if (streams_used) {
-      (void)hipStreamSynchronize(d->table_stream);
-      for (hipStream_t x : d->same_st)
-        if (x) (void)hipStreamSynchronize(x);
-    }
-  }
-  if (rc == BLSGPU_OK) {  // results reach the caller only when every one of them was computed
-    if (n) memcpy(set_result, h_set.data(), n);
-    if (group_result) memcpy(group_result, h_grp.data(), G);
-    if (stats) *stats = st;
-  }
-  leave(ctx);
-  return rc;
-}
-
-int blsgpu_key_validate(blsgpu_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_t pk_len, uint32_t stride,
-                        uint8_t* out96, int8_t* status) {
-  if (!ctx || ctx->devs.empty() || !pks || !status || stride < pk_len) return BLSGPU_ERR_ARGS;
-  if (pk_len != 48 && pk_len != 96) return BLSGPU_ERR_ARGS;
-  if (n == 0) return BLSGPU_OK;
-  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
-  Device* d = ctx->devs[0];
-  int rc = BLSGPU_OK;
-  try {
-    std::lock_guard<std::mutex> hl(d->helper_mu);
-    HIPCHK(hipSetDevice(d->id));
-    const size_t o_out = al256((size_t)n * stride), o_st = al256(o_out + (size_t)n * 96), total = o_st + n;
-    Slot& sl = d->helper;
-    sl.d_in.ensure(total);
-    hipStream_t s = d->table_stream;
-    uint8_t* din = sl.d_in.p;
-    HIPCHK(hipMemcpyAsync(din, pks, (size_t)n * stride, hipMemcpyHostToDevice, s));
-    launch_key_validate(din, n, pk_len, stride, din + o_out, reinterpret_cast<int8_t*>(din + o_st), s);
-    HIPCHK(hipGetLastError());
-    if (out96) HIPCHK(hipMemcpyAsync(out96, din + o_out, (size_t)n * 96, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(status, din + o_st, n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-  } catch (HipError&) {
-    rc = BLSGPU_DEVICE_ERROR;
-  }
-  leave(ctx);
-  return rc;
-}
-
-int blsgpu_signing_roots(blsgpu_ctx* ctx, int kind, uint32_t n, const uint8_t* objects, uint32_t object_stride,
-                         const uint8_t* domains, uint32_t domain_stride, uint8_t* out32) {
-  if (!ctx || ctx->devs.empty() || !objects || !domains || !out32) return BLSGPU_ERR_ARGS;
-  const uint32_t obj_len = kind == BLSGPU_ROOT_OBJECT ? 32 : (kind == BLSGPU_ROOT_ATTESTATION_DATA ? 128 : 0);
-  if (!obj_len || object_stride < obj_len || (domain_stride != 0 && domain_stride < 32)) return BLSGPU_ERR_ARGS;
-  if (n == 0) return BLSGPU_OK;
-  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
-  Device* d = ctx->devs[0];
-  int rc = BLSGPU_OK;
-  try {
-    std::lock_guard<std::mutex> hl(d->helper_mu);
-    HIPCHK(hipSetDevice(d->id));
-    const size_t dom_bytes = (size_t)(domain_stride ? n : 1) * (domain_stride ? domain_stride : 32);
-    const size_t o_dom = al256((size_t)n * object_stride), o_out = al256(o_dom + dom_bytes), total = o_out + 32 * (size_t)n;
-    Slot& sl = d->helper;
-    sl.d_in.ensure(total);
-    hipStream_t s = d->table_stream;
-    uint8_t* din = sl.d_in.p;
-    HIPCHK(hipMemcpyAsync(din, objects, (size_t)n * object_stride, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(din + o_dom, domains, dom_bytes, hipMemcpyHostToDevice, s));
-    launch_signing_roots(kind, din, n, object_stride, din + o_dom, domain_stride, din + o_out, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out32, din + o_out, 32 * (size_t)n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-  } catch (HipError&) {
-    rc = BLSGPU_DEVICE_ERROR;
-  }
-  leave(ctx);
-  return rc;
-}
-
-int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint32_t in_stride, uint8_t* out,
-                    uint32_t out_stride, int32_t* status) {
-  if (!ctx || ctx->devs.empty() || !in || !out || !status) return BLSGPU_ERR_ARGS;
-  // the bytes each op reads per element and writes per element (k_debug.hip): a smaller stride is refused here, so a
-  // test hook can never read or write past its buffers on the device
-  struct OpSize {
-    int op;
-    uint32_t in, out;
-  };
-  static const OpSize kOpSizes[] = {{0, 96, 48},    {1, 194, 192},  {2, 32, 192},   {3, 288, 576},  {4, 576, 576},
-                                    {5, 104, 96},   {6, 200, 192},  {7, 64, 96},    {8, 32, 96},    {9, 200, 2880},
-                                    {10, 104, 1440}, {11, 840, 56}, {16, 576, 576}, {17, 288, 576}, {18, 384, 192}};
-  const OpSize* sz = nullptr;
-  for (const OpSize& o : kOpSizes)
-    if (o.op == op) sz = &o;
-  if (!sz || in_stride < sz->in || out_stride < sz->out) return BLSGPU_ERR_ARGS;
-  if (n == 0) return BLSGPU_OK;
-  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
-  Device* d = ctx->devs[0];
-  uint8_t *din = nullptr, *dout = nullptr;
-  int32_t* dst = nullptr;
-  int rc = BLSGPU_OK;
-  try {
-    std::lock_guard<std::mutex> hl(d->helper_mu);
-    HIPCHK(hipSetDevice(d->id));
-    hipStream_t s = d->table_stream;
-    HIPCHK(hipMalloc((void**)&din, (size_t)n * in_stride));
-    HIPCHK(hipMalloc((void**)&dout, (size_t)n * out_stride));
-    HIPCHK(hipMalloc((void**)&dst, (size_t)n * 4));
-    HIPCHK(hipMemcpyAsync(din, in, (size_t)n * in_stride, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(dout, 0, (size_t)n * out_stride, s));
-    launch_debug_op(op, n, din, in_stride, dout, out_stride, dst, s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dout, (size_t)n * out_stride, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(status, dst, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-  } catch (HipError&) {
-    rc = BLSGPU_DEVICE_ERROR;
-  }
-  if (din) (void)hipFree(din);
-  if (dout) (void)hipFree(dout);
-  if (dst) (void)hipFree(dst);
-  leave(ctx);
-  return rc;
 }
 
 }  // extern "C"
