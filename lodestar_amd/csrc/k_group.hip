@@ -87,6 +87,19 @@ STAGE_KERNEL void k_f_gather(PipelineBuffers b, const uint32_t* f_ranges, uint32
   F_out[q] = a < e ? b.f_chunk[(size_t)w * b.n + a] : (w < BLS_NL ? FP_ONE.l[w] : 0u);
 }
 
+// Step segments (miller_plan.hpp): the tree above ran per (group, segment) and k_f_gather collected the heads, head of
+// (segment j, group g) in column j * ng + g of H (stride n_segs * ng).  One lane per group folds its heads by the
+// Horner pass (pairing.hpp miller_seg_fold: at most 63 - dbl[0] squarings and n_segs - 1 products) into the F_g the
+// group check reads.  One lane, not a cooperative workgroup: the fold runs on merged runs, beside other runs' one-
+// wave-per-SIMD stage kernels, where a multi-wave workgroup waits for free SIMDs of one CU (k_group_sig_miller_lane
+// below) while a single wave takes any.
+STAGE_KERNEL_W(BLSGPU_WPE_GRP) void k_f_fold(const uint32_t* H, uint32_t ng, MillerSegs sg, uint32_t* F_out) {
+  const uint32_t g = blockIdx.x * WAVE + threadIdx.x;
+  if (g >= ng) return;
+  const uint32_t stride = sg.n * ng;
+  st_fp12(F_out, ng, g, miller_seg_fold(sg.n, sg.dbl, [&](uint32_t j) { return ld_fp12(H, stride, j * ng + g); }));
+}
+
 // One 128-lane workgroup per group: the Miller loop and the final exponentiation run as cooperative Fp12
 // arithmetic (gt_wave.hpp), one Fp product per lane per step.
 //   G_in == nullptr: FinalExp(F * MillerLoop(-g1, S)) == 1 (the fallback's per-job / sub-group checks);
@@ -326,13 +339,19 @@ void launch_group_reduce(const PipelineBuffers& b, const uint32_t* f_ranges, uin
 }
 void launch_group_tree(const PipelineBuffers& b, const uint32_t* f_ranges, uint32_t ng, const uint32_t* runs,
                        uint32_t n_runs, const uint32_t* pairs, const std::vector<uint32_t>& level_end, uint32_t* F,
-                       hipStream_t s) {
+                       hipStream_t s, const MillerSegs* segs, uint32_t* H) {
   if (!ng) return;
   if (n_runs) hipLaunchKernelGGL(k_f_runs, grid_for(n_runs), dim3(WAVE), 0, s, b, runs, n_runs);
   uint32_t p0 = 0;
   for (const uint32_t p1 : level_end) {
     if (p1 > p0) hipLaunchKernelGGL(k_f_pairs, dim3(p1 - p0), dim3(GTW_LANES), 0, s, b, pairs + 2 * (size_t)p0);
     p0 = p1;
+  }
+  if (segs && segs->n > 1) {  // the heads of every (segment, group), then the fold per group
+    const uint32_t nh = segs->n * ng;
+    hipLaunchKernelGGL(k_f_gather, grid_for(nh * W_FP12), dim3(WAVE), 0, s, b, f_ranges, nh, H);
+    hipLaunchKernelGGL(k_f_fold, grid_for(ng), dim3(WAVE), 0, s, H, ng, *segs, F);
+    return;
   }
   hipLaunchKernelGGL(k_f_gather, grid_for(ng * W_FP12), dim3(WAVE), 0, s, b, f_ranges, ng, F);
 }

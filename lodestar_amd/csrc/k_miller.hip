@@ -8,8 +8,11 @@
 //                   (P = r_i pk_i) or, with same-message merging, a unit: the included sets of one batch
 //                   group that sign the same root (P = sum r_i pk_i; the pairing is bilinear, so
 //                   prod_i e(r_i pk_i, H(m)) = e(sum_i r_i pk_i, H(m))).
+//                   Runs of >= 65,536 items (miller_plan.hpp): chunks of 8 with J lanes per chunk, lane (chunk,
+//                   segment j) over its own contiguous step range from f = 1; k_group.hip k_f_fold puts the J values
+//                   of a group together (f = prod_j g_j^(2^(doubling steps after segment j))).
 //   k_miller_acc2:  the same accumulation on TWO lanes per chunk, each holding half of f (no spills): the default
-//                   for one-item chunks (runs below 131,072 pairings); chunks of >= 2 stay on one lane (faster).
+//                   for one-item chunks (runs below 65,536 pairings); chunks of >= 2 stay on one lane (faster).
 //   k_miller_lines2 (lane pairs, fp2x.hpp) and k_miller_coop (one 192-lane workgroup per pairing, small runs).
 // Line traffic is 68 x 84 words = 22.8 KB per message (HBM-cheap next to ~5,200 Montgomery products).
 #include "k_common.hpp"
@@ -135,25 +138,44 @@ STAGE_KERNEL_W(BLSGPU_WPE_LINES2) void k_miller_lines2(PipelineBuffers b) {
 // doubling step for the whole chunk (the multi-pairing form of blst's miller_loop_n): K items cost
 // 63 squarings + 68 K line multiplications instead of K (63 + 68).  UNITS: item u is pairing unit u
 // (P = unit_p[u]); otherwise item i is a set (P = r_i pk_i, only if it enters the batch equation).
-template <bool UNITS>
-STAGE_KERNEL_W(BLSGPU_WPE_ACC) void k_miller_acc(PipelineBuffers b) {
+//
+// SEG (step segments, miller_plan.hpp): the grid is (chunk blocks, segments); a block's segment is wave-uniform, so the
+// lanes of a wave run the same steps and read the same line rows.  The lane replays the schedule up to its first step
+// (a doubling step: add_next is false there), runs its own steps from f = 1 without the squaring of the first, as step
+// 0 does, and stores conj(f) at slot segment * n_chunks + c; k_f_fold (k_group.hip) puts the segments together.
+// Without SEG the steps are the constants 0 .. 68 and the slot is c: the kernel of one-segment runs.
+template <bool UNITS, bool SEG>
+STAGE_KERNEL_W(BLSGPU_WPE_ACC) void k_miller_acc(PipelineBuffers b, MillerSegs sg) {
   const uint32_t c = blockIdx.x * WAVE + threadIdx.x;
   if (c >= b.n_chunks) return;
   const uint32_t k0 = b.chunk_first[c], k1 = b.chunk_first[c + 1];
+  int s0 = 0, s1 = MILLER_STEPS, bit = 62;
+  bool add_next = false;
+  if (SEG) {
+    s0 = (int)sg.first[blockIdx.y];
+    s1 = (int)sg.first[blockIdx.y + 1];
+#pragma unroll 1
+    for (int s = 0; s < s0; s++) {
+      if (!add_next) {
+        add_next = (BLS_Z_ABS >> bit) & 1ull;
+        bit--;
+      } else {
+        add_next = false;
+      }
+    }
+  }
 #if ACC_PREFETCH
   __shared__ uint32_t pre[W_LINE * WAVE];
   auto msg_of = [&](uint32_t k) {
     const uint32_t i = b.chunk_items[k];
     return UNITS ? b.unit_msg[i] : b.msg_idx[i];
   };
-  if (k1 > k0) line_prefetch(pre, b.lines, b.nm, msg_of(k0));
+  if (k1 > k0) line_prefetch(pre, b.lines + (size_t)s0 * W_LINE * b.nm, b.nm, msg_of(k0));
 #endif
   fp12 f = fp12_one();
-  int bit = 62;
-  bool add_next = false;
 #pragma unroll 1
-  for (int s = 0; s < MILLER_STEPS; s++) {
-    if (!add_next && s != 0) f = fp12_sqr(f);
+  for (int s = s0; s < s1; s++) {
+    if (!add_next && s != s0) f = fp12_sqr(f);
     const uint32_t* o = b.lines + (size_t)s * W_LINE * b.nm;
 #if BLS_LINE_PAIRS
     // the chunk's lines two at a time: their product first (line_pair, 6 Fp2 products), then f times it (17) -- 23
@@ -183,7 +205,7 @@ STAGE_KERNEL_W(BLSGPU_WPE_ACC) void k_miller_acc(PipelineBuffers b) {
       line_read_done();
       if (k + 1 < k1)
         line_prefetch(pre, o, b.nm, msg_of(k + 1));
-      else if (s + 1 < MILLER_STEPS)
+      else if (s + 1 < s1)
         line_prefetch(pre, o + (size_t)W_LINE * b.nm, b.nm, msg_of(k0));
       if (!active || (b.mflags[m] & MF_H_INF)) continue;
       const g1a P = ld_g1a(UNITS ? b.unit_p : b.pk_aff, b.n, i);
@@ -220,7 +242,7 @@ STAGE_KERNEL_W(BLSGPU_WPE_ACC) void k_miller_acc(PipelineBuffers b) {
       add_next = false;
     }
   }
-  st_fp12(b.f_chunk, b.n, c, fp12_conj(f));
+  st_fp12(b.f_chunk, b.n, SEG ? blockIdx.y * b.n_chunks + c : c, fp12_conj(f));
 }
 
 // Mid-size runs (latency with the chip not filled by one lane per pairing): TWO lanes per pairing, lane h of the
@@ -572,10 +594,19 @@ void launch_miller_accx(const PipelineBuffers& b, bool units, hipStream_t s) {
   else
     hipLaunchKernelGGL(k_miller_accx<false>, grid_for(2 * b.n_chunks), dim3(WAVE), 0, s, b);
 }
-void launch_miller_acc(const PipelineBuffers& b, bool units, hipStream_t s) {
+void launch_miller_acc(const PipelineBuffers& b, bool units, hipStream_t s, const MillerSegs* segs) {
   if (!b.n_chunks) return;
+  if (segs && segs->n > 1) {  // one block row per segment
+    const dim3 grid(grid_for(b.n_chunks).x, segs->n);
+    if (units)
+      hipLaunchKernelGGL((k_miller_acc<true, true>), grid, dim3(WAVE), 0, s, b, *segs);
+    else
+      hipLaunchKernelGGL((k_miller_acc<false, true>), grid, dim3(WAVE), 0, s, b, *segs);
+    return;
+  }
+  const MillerSegs one{};
   if (units)
-    hipLaunchKernelGGL(k_miller_acc<true>, grid_for(b.n_chunks), dim3(WAVE), 0, s, b);
+    hipLaunchKernelGGL((k_miller_acc<true, false>), grid_for(b.n_chunks), dim3(WAVE), 0, s, b, one);
   else
-    hipLaunchKernelGGL(k_miller_acc<false>, grid_for(b.n_chunks), dim3(WAVE), 0, s, b);
+    hipLaunchKernelGGL((k_miller_acc<false, false>), grid_for(b.n_chunks), dim3(WAVE), 0, s, b, one);
 }

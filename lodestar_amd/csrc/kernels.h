@@ -129,7 +129,16 @@ void launch_miller_lines2(const PipelineBuffers& b, hipStream_t s);
 // Miller values of the chunks (items are units when `units`, else sets): f_chunk[c] = prod over the chunk's
 // active items of MillerLoop(P_item, H(m_item)), one lane per chunk, the Fp12 squarings shared
 void launch_miller_accx(const PipelineBuffers& b, bool units, hipStream_t s);
-void launch_miller_acc(const PipelineBuffers& b, bool units, hipStream_t s);
+// Step segments of the one-lane accumulation (miller_plan.hpp): segment j covers steps [first[j], first[j + 1]) and
+// holds dbl[j] doubling steps.  With n > 1 lane (chunk c, segment j) writes the value of its own steps to slot
+// j * n_chunks + c of f_chunk (n * n_chunks <= the stride); launch_group_fold puts the groups' segment heads together.
+#define MILLER_MAX_SEGS 8
+struct MillerSegs {
+  uint32_t n;
+  uint32_t first[MILLER_MAX_SEGS + 1];
+  uint32_t dbl[MILLER_MAX_SEGS];
+};
+void launch_miller_acc(const PipelineBuffers& b, bool units, hipStream_t s, const MillerSegs* segs = nullptr);
 // the same for chunks of ONE item each, two lanes per pairing (k_miller.hip k_miller_acc2: mid-size runs, latency)
 void launch_miller_acc2(const PipelineBuffers& b, bool units, hipStream_t s);
 // the same on SIX lanes per chunk, one w-basis Fp2 coefficient of f per lane (k_miller_acc6: 2k-16k-pairing runs)
@@ -150,9 +159,12 @@ void launch_group_reduce(const PipelineBuffers& b, const uint32_t* f_ranges, uin
 // the same F_g as a product tree (k_group.hip): runs[0 .. n_runs) (first, end) chunk runs multiplied lane-serially
 // into their first chunk, then the pair levels (pairs up to level_end[0], then up to level_end[1], ...: f[dst] *=
 // f[src], one cooperative workgroup per pair), then F_g = f[first chunk of g]
+// (segs with n > 1: the tree was planned per (segment, group) over the segment-major slots and f_ranges holds
+// segs->n * n_groups ranges, range j * n_groups + g = group g's slots of segment j; their heads go to H (W_FP12 SoA,
+// stride segs->n * n_groups) and F_g is their Horner fold, k_group.hip k_f_fold)
 void launch_group_tree(const PipelineBuffers& b, const uint32_t* f_ranges, uint32_t n_groups, const uint32_t* runs,
                        uint32_t n_runs, const uint32_t* pairs, const std::vector<uint32_t>& level_end, uint32_t* F,
-                       hipStream_t s);
+                       hipStream_t s, const MillerSegs* segs = nullptr, uint32_t* H = nullptr);
 // check: ok_g = FinalExp(F_g * MillerLoop(-g1, S_g)) == 1
 // (sel: check only the entries sel[0 .. n_sel), verdict q -> ok[q])
 // (G: MillerLoop(-g1, S_g) precomputed by launch_group_sig_miller, W_FP12 SoA stride n_groups; null = computed here)

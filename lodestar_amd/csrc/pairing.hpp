@@ -159,6 +159,23 @@ BLS_FN fp12 miller_acc_step(const fp12& f, int s, bool is_add, const line3& L, c
   return fp12_mul_by_014(g, L.l0, fp2_mul_fp(L.c1, xP), fp2_mul_fp(L.c4, yP));
 }
 
+// Step segments (miller_plan.hpp): the accumulation over steps [first_j, first_j+1) from f = 1, the squaring of the
+// segment's first (doubling) step skipped, gives g_j with f = prod_j g_j^(2^(e_j)), e_j = the doubling steps of the
+// later segments.  The Horner pass: R = g_0; R = R^(2^(dbl[j])) g_j for j = 1 .. n_segs - 1, dbl[j] = the doubling
+// steps of segment j (its first one included).  conj commutes with it, so it folds the stored conj(g_j) alike.
+// ld(j) returns g_j.
+template <class Ld>
+BLS_FN fp12 miller_seg_fold(uint32_t n_segs, const uint32_t* dbl, Ld ld) {
+  fp12 R = ld(0u);
+#pragma unroll 1
+  for (uint32_t j = 1; j < n_segs; j++) {
+#pragma unroll 1
+    for (uint32_t t = 0; t < dbl[j]; t++) R = fp12_sqr(R);
+    R = fp12_mul(R, ld(j));
+  }
+  return R;
+}
+
 // f = conj(f_{|z|,Q}(P)).  P, Q affine and not infinity.
 // The 68 steps (63 doublings, 5 additions) run as one flat loop with a single copy of each step body:
 // a doubling step squares f first (except the very first), an addition step does not.

@@ -27,6 +27,7 @@
 #include <system_error>
 
 #include "runtime_internal.hpp"
+#include "miller_plan.hpp"
 
 using namespace blsgpu_rt;
 
@@ -56,7 +57,10 @@ struct GroupPlanEntry {
 // pairing vs 5,162 at k = 1, lodestar_amd/op_counts.json) but leave n / k lanes.  The accumulation is one wave per
 // SIMD, so k doubles only while n / 2k still gives every SIMD a wave (>= 65,536 lanes = 1,024 waves): below that
 // the stage would hold fewer SIMDs for longer on the run's critical path (r03c trace: k = 2 at 54k sets held 341
-// waves for 14 ms).
+// waves for 14 ms).  This is the rule of whole-loop lanes (one segment): runs below 65,536 items, the fallback's own
+// accumulations and every run the step-segment plan leaves alone.  From 65,536 items on, run_shard asks
+// miller_plan::plan_auto for (k, J): J lanes per chunk, each over its own step range, keep the lane count of a J
+// times smaller k, so such runs take k = 8 (or 4) at the lane count that stopped this rule at 1 or 2.
 inline uint32_t miller_k_auto(uint32_t n_items) {
   uint32_t k = 1;
   while (k < 4 && n_items / (2 * k) >= 65536) k *= 2;
@@ -66,34 +70,27 @@ inline uint32_t miller_k_auto(uint32_t n_items) {
 // The Miller accumulation of a run's chunks: six lanes per chunk (k_miller_acc6) for runs of one-item chunks up to
 // acc6_max chunks, two lanes (k_miller_acc2) for larger one-item-chunk runs while one lane per chunk would leave SIMDs
 // idle (< 65,536 chunks = 1,024 waves), else one lane per chunk.
-void launch_miller_acc_auto(const PipelineBuffers& pb, bool units, hipStream_t st, uint32_t mk, int64_t lanes_opt,
-                            int64_t acc6_max, bool pairs) {
-  if (lanes_opt == 6 || (lanes_opt == 0 && mk == 1 && (int64_t)pb.n_chunks <= acc6_max)) {
-    launch_miller_acc6(pb, units, st);
-    return;
-  }
-  if (lanes_opt == 3 || (lanes_opt == 0 && pairs)) {  // lane pairs, every Fp2 split (gtx.hpp): two waves per SIMD
-    launch_miller_accx(pb, units, st);
-    return;
-  }
+enum class AccForm { six, pairs, two, one };
+inline AccForm acc_form(uint32_t mk, uint32_t n_chunks, int64_t lanes_opt, int64_t acc6_max, bool pairs) {
+  if (lanes_opt == 6 || (lanes_opt == 0 && mk == 1 && (int64_t)n_chunks <= acc6_max)) return AccForm::six;
+  // lane pairs, every Fp2 split (gtx.hpp): two waves per SIMD
+  if (lanes_opt == 3 || (lanes_opt == 0 && pairs)) return AccForm::pairs;
   // two lanes per chunk: f never on one lane, no spills (r4zd/r4ze A/B, PMC r4f); auto: one-item chunks
-  const bool two = lanes_opt == 2 || (lanes_opt == 0 && mk == 1);
-  if (two)
-    launch_miller_acc2(pb, units, st);
-  else
-    launch_miller_acc(pb, units, st);
+  return lanes_opt == 2 || (lanes_opt == 0 && mk == 1) ? AccForm::two : AccForm::one;
+}
+// (segs: step segments, one-lane form only)
+void launch_miller_acc_auto(const PipelineBuffers& pb, bool units, hipStream_t st, uint32_t mk, int64_t lanes_opt,
+                            int64_t acc6_max, bool pairs, const MillerSegs* segs = nullptr) {
+  switch (acc_form(mk, pb.n_chunks, lanes_opt, acc6_max, pairs)) {
+    case AccForm::six: launch_miller_acc6(pb, units, st); break;
+    case AccForm::pairs: launch_miller_accx(pb, units, st); break;
+    case AccForm::two: launch_miller_acc2(pb, units, st); break;
+    case AccForm::one: launch_miller_acc(pb, units, st, segs); break;
+  }
 }
 
-// Splits item ranges into Miller chunks of <= k items: appends to first/items, returns [chunk_begin, end)
-inline std::pair<uint32_t, uint32_t> add_chunks(std::vector<uint32_t>& first, std::vector<uint32_t>& items,
-                                                uint32_t a, uint32_t e, uint32_t k, const uint32_t* map = nullptr) {
-  const uint32_t c0 = (uint32_t)first.size() - 1;
-  for (uint32_t x = a; x < e; x += k) {
-    for (uint32_t y = x; y < std::min(e, x + k); y++) items.push_back(map ? map[y] : y);
-    first.push_back((uint32_t)items.size());
-  }
-  return {c0, (uint32_t)first.size() - 1};
-}
+using miller_plan::add_chunks;  // item ranges -> Miller chunks of <= k items (miller_plan.hpp)
+static_assert(miller_plan::kSteps == MILLER_STEPS && miller_plan::kMaxSegments == MILLER_MAX_SEGS, "miller_plan.hpp");
 
 // Splits set ranges into MSM slices of <= len (<= MSM_SLICE) sets: appends to slices (pairs), returns the range's
 // [first slice, end slice)
@@ -404,17 +401,56 @@ int run_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_
   // (an urgent run takes the padding only with urgent_excl: on a small CU partition, or beside throughput runs, a
   // workgroup that needs a whole CU waits for one)
   const bool excl = BLSGPU_EXCLUSIVE_SMALL && n_items <= (uint32_t)opt.coop_excl_max && (!sl.urgent || opt.urgent_excl);
-  const uint32_t mk = coop ? 1u : opt.miller_k > 0 ? (uint32_t)opt.miller_k : miller_k_auto(n_items);
+  // mk_whole: the items per chunk of whole-loop lanes (one step segment), which the fallback's own accumulations keep
+  const uint32_t mk_whole = coop ? 1u : opt.miller_k > 0 ? (uint32_t)opt.miller_k : miller_k_auto(n_items);
+  auto group_items = [&](uint32_t g) -> std::pair<uint32_t, uint32_t> {
+    if (merged) return {g_unit_first[g], g_unit_first[g + 1]};
+    return {job_sets(group_jobs[g].first).first, job_sets(group_jobs[g].second - 1).second};
+  };
+  // Step segments (miller_plan.hpp): a run of >= 65,536 items that would take the one-lane or two-lane chunk form takes
+  // chunks of 8 (or 4) items on the one-lane kernel with J lanes per chunk, each over its own step range, so that
+  // n_chunks J lanes still give every SIMD a wave; the F tree then runs per (group, segment) and k_f_fold folds the J
+  // heads of a group.  Such a run no longer has one chunk per set, so it gives up keep_f (below): a failed group's
+  // jobs re-run their Miller loops; while the device sees enough invalid sets to fail a fifth of the groups, a run
+  // that would keep its per-set values stays as it is (miller_plan::hold_kept_values).
+  // BLSGPU_MILLER_SEGMENTS = J (diagnostics) switches the rule off: the one-lane form then runs min(J, k) segments
+  // at any run size, every other form as ever.
+  const AccForm form_whole = acc_form(mk_whole, n_items, opt.miller_lanes, opt.acc6_max, opt.miller_pairs != 0);
+  uint32_t mk = mk_whole, segs = 1;
+  bool seg_plan = false;  // the automatic rule chose (mk, segs): the batch pass takes the one-lane kernel
+  if (opt.miller_segments > 0) {
+    if (!coop && form_whole == AccForm::one) segs = (uint32_t)std::min<int64_t>(opt.miller_segments, mk);
+  } else if (!coop && opt.miller_lanes == 0 && (form_whole == AccForm::one || form_whole == AccForm::two)) {
+    std::vector<uint32_t> g_len(ng0);
+    for (uint32_t g = 0; g < ng0; g++) g_len[g] = group_items(g).second - group_items(g).first;
+    bool hold = false;  // many failing groups: the kept per-set Miller values are worth more than the plan
+    if (opt.keep_f && !merged && mk_whole == 1 && ng0) {
+      std::lock_guard<std::mutex> lk(d.fail_mu);
+      hold = miller_plan::hold_kept_values(d.fail_rate, (double)n / ng0);
+    }
+    const miller_plan::Plan pl =
+        miller_plan::plan_auto(n_items, g_len.data(), ng0, stride, opt.miller_k > 0 || hold, mk_whole);
+    seg_plan = pl.k != mk_whole || pl.segs > 1;
+    mk = pl.k, segs = pl.segs;
+  }
+  const bool interleave = segs > 1 || seg_plan;  // (a one-segment run outside the rule keeps consecutive items)
   std::vector<uint32_t> chunk_first{0}, chunk_items, g_chunks(2 * (size_t)ng0);
   chunk_items.reserve(n);
   for (uint32_t g = 0; g < ng0; g++) {
-    const uint32_t a = merged ? g_unit_first[g] : job_sets(group_jobs[g].first).first;
-    const uint32_t e = merged ? g_unit_first[g + 1] : job_sets(group_jobs[g].second - 1).second;
-    const auto cr = add_chunks(chunk_first, chunk_items, a, e, mk);
+    const auto ae = group_items(g);
+    const auto cr = add_chunks(chunk_first, chunk_items, ae.first, ae.second, mk, interleave);
     g_chunks[2 * g] = cr.first;
     g_chunks[2 * g + 1] = cr.second;
   }
   const uint32_t n_chunks = (uint32_t)chunk_first.size() - 1;
+  segs = miller_plan::fit_segments(n_chunks, segs, stride);  // slot j * n_chunks + c of f_chunk (stride words apart)
+  MillerSegs msegs{};
+  {
+    const miller_plan::Segments sg = miller_plan::segments(segs);
+    msegs.n = sg.n;
+    for (uint32_t j = 0; j <= sg.n; j++) msegs.first[j] = sg.first[j];
+    for (uint32_t j = 0; j < sg.n; j++) msegs.dbl[j] = sg.dbl[j];
+  }
   // Per-set pairings (no same-message units, one item per chunk): chunk c is set c (the groups cover every set of a
   // non-empty job, in order), so the batch pass's Miller values f_c = MillerLoop(r_c pk_c, H(m_c)) are exactly what a
   // failed group's per-job checks need.  They are copied aside before the F tree multiplies chunks in place, and the
@@ -462,22 +498,31 @@ int run_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_
   // ftree = runs, then the pairs.  Up to 16384 chunks (a 16k call) the tree starts at the chunks: its latency.
   std::vector<uint32_t> ftree, f_level_end;
   uint32_t f_k = 1, f_max = 0;
-  if (n_chunks > 16384)
+  // With step segments the tree runs per (segment, group) over the segment-major slots: range j * ng0 + g = the
+  // slots j * n_chunks + (group g's chunks); one segment: the groups' chunk ranges themselves.
+  const uint32_t n_slots = n_chunks * segs, n_franges = ng0 * segs;
+  std::vector<uint32_t> f_rng(2 * (size_t)n_franges);
+  for (uint32_t j = 0; j < segs; j++)
+    for (uint32_t g = 0; g < ng0; g++) {
+      f_rng[2 * ((size_t)j * ng0 + g)] = j * n_chunks + g_chunks[2 * g];
+      f_rng[2 * ((size_t)j * ng0 + g) + 1] = j * n_chunks + g_chunks[2 * g + 1];
+    }
+  if (n_slots > 16384)
     for (const uint32_t heads = opt.f_run_max > 16 ? 256u : 8192u;
-         n_chunks / f_k > heads && f_k < (uint32_t)opt.f_run_max;)
+         n_slots / f_k > heads && f_k < (uint32_t)opt.f_run_max;)
       f_k *= 2;
   for (uint32_t g = 0; g < ng0; g++) f_max = std::max(f_max, g_chunks[2 * g + 1] - g_chunks[2 * g]);
   if (f_k > 1)
-    for (uint32_t g = 0; g < ng0; g++)
-      for (uint32_t x = g_chunks[2 * g], e = g_chunks[2 * g + 1]; x < e; x += f_k)
+    for (uint32_t r = 0; r < n_franges; r++)
+      for (uint32_t x = f_rng[2 * r], e = f_rng[2 * r + 1]; x < e; x += f_k)
         if (std::min(e, x + f_k) - x > 1) {
           ftree.push_back(x);
           ftree.push_back(std::min(e, x + f_k));
         }
   const uint32_t n_fruns = (uint32_t)(ftree.size() / 2);
   for (uint32_t st = f_k; st < f_max; st *= 2) {
-    for (uint32_t g = 0; g < ng0; g++)
-      for (uint32_t i = g_chunks[2 * g], e = g_chunks[2 * g + 1]; i + st < e; i += 2 * st) {
+    for (uint32_t r = 0; r < n_franges; r++)
+      for (uint32_t i = f_rng[2 * r], e = f_rng[2 * r + 1]; i + st < e; i += 2 * st) {
         ftree.push_back(i);
         ftree.push_back(i + st);
       }
@@ -504,7 +549,7 @@ int run_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_
                o_siglen = al256(o_sigs + (size_t)n * sig_w), o_umsg = al256(o_siglen + (size_t)n * 4),
                o_midx = al256(o_umsg + (size_t)n_umsg * 32), o_ranges = al256(o_midx + (size_t)n * 4),
                o_franges = al256(o_ranges + (size_t)std::max(ng0, 1u) * 8),
-               o_ufirst = al256(o_franges + (size_t)std::max(ng0, 1u) * 8),
+               o_ufirst = al256(o_franges + (size_t)std::max(n_franges, 1u) * 8),
                o_usets = al256(o_ufirst + (size_t)(n_units + 1) * 4), o_umsgi = al256(o_usets + (size_t)unit_sets.size() * 4),
                o_cfirst = al256(o_umsgi + (size_t)n_units * 4), o_citems = al256(o_cfirst + (size_t)(n_chunks + 1) * 4),
                o_agg = al256(o_citems + chunk_items.size() * 4), o_slices = al256(o_agg + agg_sets.size() * 4),
@@ -552,9 +597,8 @@ int run_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_
   for (uint32_t g = 0; g < ng0; g++) {
     hranges[2 * g] = job_sets(group_jobs[g].first).first;
     hranges[2 * g + 1] = job_sets(group_jobs[g].second - 1).second;
-    hfranges[2 * g] = g_chunks[2 * g];
-    hfranges[2 * g + 1] = g_chunks[2 * g + 1];
   }
+  memcpy(hfranges, f_rng.data(), f_rng.size() * 4);
   memcpy(hin + o_cfirst, chunk_first.data(), chunk_first.size() * 4);
   memcpy(hin + o_citems, chunk_items.data(), chunk_items.size() * 4);
   if (!agg_sets.empty()) memcpy(hin + o_agg, agg_sets.data(), agg_sets.size() * 4);
@@ -597,6 +641,7 @@ int run_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_
   sl.d_work.ensure((size_t)stride * per_set + (size_t)nm * (W_G2A + W_G2J + W_FP + 14 * W_FP + 2 * W_G2J));
   sl.d_lines.ensure((size_t)nm * kMillerLineWords);
   if (keep_f) sl.d_fkeep.ensure((size_t)stride * W_FP12);
+  if (segs > 1) sl.d_fseg.ensure((size_t)W_FP12 * n_franges);
   if (rsig_spec) sl.d_fb.ensure((size_t)stride * 9 * W_G2J);
   uint8_t* const din = sl.d_in.p;
   uint8_t* const d_ok0 = sl.d_res.p + o_ok;
@@ -688,8 +733,9 @@ int run_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_
     if (host_trace())
       fprintf(stderr,
               "[blsgpu host] run %u sets: merge %.2f ms, prep %.2f ms (dedupe %.2f, structure %.2f), pick-to-copy %.2f "
-              "ms, %zu B in\n",
-              n, tl_merge_ms, ms_since(t_prep0), t_dedupe_ms, t_struct_ms, ms_since(tl_run_t0), in_bytes);
+              "ms, %zu B in, %u Miller chunks of %u x %u segments\n",
+              n, tl_merge_ms, ms_since(t_prep0), t_dedupe_ms, t_struct_ms, ms_since(tl_run_t0), in_bytes, n_chunks, mk,
+              segs);
     // The input copy goes on the run's signature stream, or (copy_stream, when none of the run's buffers was
     // reallocated in that stream's order) on the device's table stream: a previous run's tail still queued on the
     // signature stream of this pair then delays only this run's signature branch, not its message branch
@@ -766,8 +812,10 @@ int run_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_
     if (merged) launch_unit_aggregate(pb, sm);
     if (coop)
       launch_miller_coop(pb, merged, sm, excl);
+    else if (seg_plan)
+      launch_miller_acc(pb, merged, sm, &msegs);
     else
-      launch_miller_acc_auto(pb, merged, sm, mk, opt.miller_lanes, opt.acc6_max, opt.miller_pairs != 0);
+      launch_miller_acc_auto(pb, merged, sm, mk, opt.miller_lanes, opt.acc6_max, opt.miller_pairs != 0, &msegs);
     end(5, sm);
     if (keep_f && opt.keep_copy == 1)
       launch_copy_words(sl.d_fkeep.p, pb.f_chunk, (size_t)stride * W_FP12, sm);
@@ -776,7 +824,8 @@ int run_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_
     const uint32_t* d_franges = reinterpret_cast<uint32_t*>(din + o_franges);
     beg(6, sm);
     const uint32_t* d_ftree = reinterpret_cast<uint32_t*>(din + o_ftree);
-    launch_group_tree(pb, d_franges, ng0, d_ftree, n_fruns, d_ftree + 2 * (size_t)n_fruns, f_level_end, sl.d_F.p, sm);
+    launch_group_tree(pb, d_franges, ng0, d_ftree, n_fruns, d_ftree + 2 * (size_t)n_fruns, f_level_end, sl.d_F.p, sm,
+                      &msegs, sl.d_fseg.p);
     end(6, sm);
     HIPCHK(hipEventRecord(sl.join_msg, sm));
     if (spec)
@@ -940,7 +989,7 @@ int run_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_
         rf[2 * q + 1] = js.second;
         continue;
       }
-      const auto cr = add_chunks(rfirst, ritems, js.first, js.second, mk);
+      const auto cr = add_chunks(rfirst, ritems, js.first, js.second, mk_whole);
       rf[2 * q] = cr.first;
       rf[2 * q + 1] = cr.second;
     }
@@ -1023,7 +1072,7 @@ int run_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_
       if (coop)  // no stored lines in a cooperative run: the per-job chunks hold one set each (mk = 1)
         launch_miller_coop(pr, false, sfb);
       else
-        launch_miller_acc_auto(pr, false, sfb, mk, opt.miller_lanes, opt.acc6_max, opt.miller_pairs != 0);
+        launch_miller_acc_auto(pr, false, sfb, mk_whole, opt.miller_lanes, opt.acc6_max, opt.miller_pairs != 0);
     }
     st.fallback_jobs += nr;
     if (small_jobs) {
@@ -2112,6 +2161,12 @@ int blsgpu_init(const int* devices, int n_devices, blsgpu_ctx** out) {
   blsgpu_ctx* ctx = new blsgpu_ctx();
   ctx->hw_queues = hw_queues_of_process();
   ctx->slots_per_device = default_slots(ctx->hw_queues);
+  // diagnostics / tests: BLSGPU_MILLER_SEGMENTS = J forces the one-lane accumulation's step segments (run_shard);
+  // unset, 0 or anything else: by run size
+  if (const char* v = getenv("BLSGPU_MILLER_SEGMENTS")) {
+    const long j = strtol(v, nullptr, 10);
+    if (j >= 1 && j <= MILLER_MAX_SEGS) ctx->opt.miller_segments = j;
+  }
   try {
     for (int id : ids) {
       Device* d = new Device();

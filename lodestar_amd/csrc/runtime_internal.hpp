@@ -183,6 +183,7 @@ struct Slot {
   DevBuf<uint8_t> d_in, d_res, d_bytes, d_ok, d_fbflags;
   DevBuf<uint32_t> d_work, d_lines, d_S, d_F, d_G, d_list, d_msmB, d_msmW, d_fb;
   DevBuf<uint32_t> d_fkeep;  // the batch pass's per-set Miller values, kept for the fallback (run_shard keep_f)
+  DevBuf<uint32_t> d_fseg;   // step segments: the (segment, group) heads of the F tree before their fold (k_f_fold)
   HostBuf<uint8_t> h_in, h_res, h_ok;
   HostBuf<uint32_t> h_list;
   // The slot's own stream for the fallback of its runs (lowest priority).  A failed group's checks used to run on the
@@ -198,12 +199,12 @@ struct Slot {
   // whenever it grows a buffer (its dispatcher waits for each run), so only this ordering matters
   void set_stream(hipStream_t st) {
     for (auto* b : {&d_in, &d_res, &d_bytes, &d_ok, &d_fbflags}) b->st = st;
-    for (auto* b : {&d_work, &d_lines, &d_S, &d_F, &d_G, &d_list, &d_msmB, &d_msmW, &d_fb, &d_fkeep}) b->st = st;
+    for (auto* b : {&d_work, &d_lines, &d_S, &d_F, &d_G, &d_list, &d_msmB, &d_msmW, &d_fb, &d_fkeep, &d_fseg}) b->st = st;
   }
   void release_all() {
     d_in.release(); d_res.release(); d_bytes.release(); d_ok.release(); d_fbflags.release();
     d_work.release(); d_lines.release(); d_S.release(); d_F.release(); d_list.release();
-    d_msmB.release(); d_msmW.release(); d_fb.release(); d_G.release(); d_fkeep.release();
+    d_msmB.release(); d_msmW.release(); d_fb.release(); d_G.release(); d_fkeep.release(); d_fseg.release();
     h_in.release(); h_res.release(); h_ok.release(); h_list.release();
   }
 };
@@ -289,6 +290,8 @@ struct Options {  // snapshot taken at the start of each call
   int64_t pipeline_depth = 3;    // runs a device has in flight (taken by a slot, batch pass not yet complete)
   int64_t group_policy = 0;    // 0 = groups of >= group_sets sets; 1 = the reference pool's jobs / requests / chunks
   bool serial = false;  // diagnostics: every branch of a run on one stream (each kernel alone on the chip)
+  int64_t miller_segments = 0;  // diagnostics (BLSGPU_MILLER_SEGMENTS, read by blsgpu_init; no option key): step
+                                // segments of the one-lane accumulation, 0 = by run size (miller_plan.hpp plan_auto)
   int64_t miller_lanes = 0;  // lanes per pairing of the one-item-chunk Miller accumulation: 0 = by run size, 1, 2
   int64_t f_run_max = 16;    // merged runs: longest lane-serial run of the F product tree before the cooperative pairs
   int64_t lane_tail_min = 0;  // runs of >= this many sets take the lane forms of the Horner passes and the groups'
@@ -326,7 +329,7 @@ struct Options {  // snapshot taken at the start of each call
                                   // §5.2: safe once outgrown buffers stay allocated, DevBuf::ensure)
   bool same_run(const struct Options& o) const {
     return group_sets == o.group_sets && profile == o.profile && dedupe == o.dedupe && miller_k == o.miller_k &&
-           group_policy == o.group_policy && serial == o.serial && miller_lanes == o.miller_lanes &&
+           group_policy == o.group_policy && serial == o.serial && miller_lanes == o.miller_lanes && miller_segments == o.miller_segments &&
            f_run_max == o.f_run_max && lane_tail_min == o.lane_tail_min &&
            lane_tail_parts == o.lane_tail_parts &&
            msm_slice_mid == o.msm_slice_mid && msm_tree == o.msm_tree &&
