@@ -16,7 +16,7 @@ LIB = os.environ.get("BLSGPU_LIB") or os.path.join(PKG, "libblsgpu.so")  # overr
 ARCH = os.environ.get("BLSGPU_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SOURCES = ["k_sig.hip", "k_msm.hip", "k_hash.hip", "k_hmap.hip", "k_pk.hip", "k_sigagg.hip", "k_awr.hip", "k_same.hip", "k_miller.hip", "k_group.hip", "k_inv.hip", "k_ssz.hip", "k_debug.hip",
-           "runtime.cpp", "helpers.cpp"]
+           "runtime.cpp", "pipeline.cpp", "helpers.cpp"]
 
 
 OBJ_DIR = os.path.join(PKG, "build")  # per-TU objects, kept so an edit rebuilds only the TUs it touches
@@ -74,11 +74,11 @@ def _headers():
 
 
 def _tu_deps(src):
-    """The host units (runtime.cpp, helpers.cpp) see only the C-ABI header, the kernel launch declarations and the
-    runtime's own headers; a kernel TU sees every arithmetic header."""
+    """The host units (runtime.cpp, pipeline.cpp, helpers.cpp) see only the C-ABI header, the kernel launch
+    declarations and the runtime's own headers; a kernel TU sees every arithmetic header."""
     if src.endswith(".cpp"):
         return [os.path.join(CSRC, f) for f in (src, "kernels.h", "batch_rand.hpp", "runtime_internal.hpp",
-                                                "helper_layout.hpp", "miller_plan.hpp")] + [
+                                                "run_plan.hpp", "helper_layout.hpp", "miller_plan.hpp")] + [
             os.path.join(ROOT, "include", "blsgpu.h")]
     return [os.path.join(CSRC, src)] + _headers()
 

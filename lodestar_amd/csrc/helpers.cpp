@@ -1,7 +1,7 @@
 // The synchronous helper calls of libblsgpu (include/blsgpu.h): aggregation, same-message verification, key
 // validation, signing roots and the debug ops.  Each runs start to finish on device 0 under Device::helper_mu, on
 // table_stream, in Device::helper's buffers; helper_call is the envelope they share and helper_layout.hpp says where
-// every field of their device arenas lies.  The asynchronous verification pipeline is runtime.cpp.
+// every field of their device arenas lies.  The asynchronous verification pipeline is runtime.cpp and pipeline.cpp.
 #include "helper_layout.hpp"
 #include "runtime_internal.hpp"
 
@@ -329,7 +329,7 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
     std::vector<uint64_t> words;
     uint64_t hash_key = 0;
     if (int e = same_begin(d, a, seed, words, hash_key)) return e;
-    // messages, deduplicated as run_shard does: group g signs unique message gmsg[g]
+    // messages, deduplicated as plan_run does (run_plan.hpp): group g signs unique message gmsg[g]
     std::vector<uint32_t> gmsg(G), uniq;
     {
       MsgIndex mi(G, hash_key ^ 0x6a09e667f3bcc908ull);

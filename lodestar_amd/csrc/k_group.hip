@@ -8,7 +8,7 @@
 //   k_group_check    one 128-lane workgroup per group: FinalExp(F * MillerLoop(-g1, S)) == 1, as
 //                    workgroup-cooperative Fp12 arithmetic (gt_wave.hpp)
 // The same two kernels re-check the sub-ranges of a failed group when the host bisects it
-// (runtime.cpp), so the fallback costs one Miller loop + final exponentiation per tested sub-range.
+// (pipeline.cpp), so the fallback costs one Miller loop + final exponentiation per tested sub-range.
 #include "k_common.hpp"
 #include "gt_wave.hpp"
 #include "gt6.hpp"
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(WAVE) void k_group_reduce(PipelineBuffers b, const 
 // products deep (2.25 ms of a 16k call's critical path, 0.8 ms of a 128-set call's).  The tree form:
 //   k_f_runs    lane per run of K consecutive chunks of a group (large runs only): their product into the run's first
 //   k_f_pairs   one 128-lane workgroup per pair (dst, src) of one tree level: f[dst] *= f[src] as a cooperative
-//               Fp12 product (gt_wave.hpp gtw_mul, ~5 us); the host plans the levels (runtime.cpp plan_f_tree)
+//               Fp12 product (gt_wave.hpp gtw_mul, ~5 us); the host plans the levels (run_plan.hpp plan_f_tree)
 //   k_f_gather  lane per (group, word): F_g = the group's first chunk (one for a group without chunks)
 STAGE_KERNEL_W(BLSGPU_WPE_GRP) void k_f_runs(PipelineBuffers b, const uint32_t* runs, uint32_t n_runs) {
   const uint32_t q = blockIdx.x * WAVE + threadIdx.x;

@@ -518,7 +518,7 @@ __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(WPE, WPE))
 // Small runs (latency): one 128-lane workgroup per pairing, the Miller loop as cooperative Fp12 arithmetic
 // (gt_wave.hpp: lines computed on the fly, one Fp product per lane per step) -- the same value as
 // k_miller_lines + k_miller_acc with one item per chunk, in ~1/6 of the time per pairing, at a fraction of the
-// lanes' efficiency; the runtime uses it only when the run's pairings fit the chip (runtime.cpp kCoopMaxItems).
+// lanes' efficiency; the runtime uses it only when the run's pairings fit the chip (run_plan.hpp Forms::coop, option coop_max).
 template <bool UNITS>
 __global__ __launch_bounds__(GTW_MILLER_LANES) void k_miller_coop(PipelineBuffers b) {
   __shared__ GtwLds sh;

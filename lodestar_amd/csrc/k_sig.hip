@@ -68,7 +68,7 @@ STAGE_KERNEL_W(BLSGPU_WPE_SUB2) void k_sig_subgroup2(PipelineBuffers b, uint32_t
 }
 
 // r_i sig_i with the batch scalar word (0 = r = 1, CoreVerify); the signed-window table goes to b.scal_tab.
-// The fallback's path for small jobs (runtime.cpp): a per-set scaling costs less than a bucket MSM per 1-3-set job.
+// The fallback's path for small jobs (pipeline.cpp run_fallback): a per-set scaling costs less than a bucket MSM per 1-3-set job.
 STAGE_KERNEL void k_sig_scale(PipelineBuffers b, uint32_t n_sets, const uint32_t* list) {
   const uint32_t q = blockIdx.x * WAVE + threadIdx.x;
   if (q >= n_sets) return;
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(WAVE) void k_sig_subgroup_coop(PipelineBuffers b, u
   }
 }
 
-// the speculative MSM's mask (runtime.cpp): the sets whose signature decoded
+// the speculative MSM's mask (pipeline.cpp enqueue_batch_pass): the sets whose signature decoded
 __global__ __launch_bounds__(WAVE) void k_spec_mask(PipelineBuffers b, uint32_t n_sets, uint8_t* spec) {
   const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
   if (i < n_sets) spec[i] = b.status[i] == BLS_OK ? 1 : 0;

@@ -1,4 +1,4 @@
-// Launchers for the verification-pipeline kernels (k_*.hip), called by runtime.cpp and helpers.cpp.
+// Launchers for the verification-pipeline kernels (k_*.hip), called by pipeline.cpp and helpers.cpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

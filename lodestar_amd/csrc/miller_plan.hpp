@@ -1,4 +1,4 @@
-// Host plan of the Miller accumulation's chunks and step segments (runtime.cpp; k_miller.hip k_miller_acc reads the
+// Host plan of the Miller accumulation's chunks and step segments (run_plan.hpp plan_run; k_miller.hip k_miller_acc reads the
 // boundaries).  No HIP here: tests/native/miller_plan_probe.cpp includes this header alone.
 //
 // The Miller value of a chunk is prod_s l_s^(2^D(s)) over the 68 steps, D(s) = the doubling steps after step s.  Cut
@@ -16,7 +16,7 @@
 
 namespace miller_plan {
 
-constexpr uint32_t kSteps = 68;                       // MILLER_STEPS (kernels.h; runtime.cpp asserts that they agree)
+constexpr uint32_t kSteps = 68;                       // MILLER_STEPS (kernels.h; pipeline.cpp asserts that they agree)
 constexpr uint32_t kDoublings = 63;                   // bits of |z| below its top bit
 constexpr uint64_t kZAbs = 0xd201000000010000ull;     // |z| (bls_constants.hpp BLS_Z_ABS)
 constexpr uint32_t kMaxSegments = 8;
@@ -77,7 +77,7 @@ inline uint32_t fit_segments(uint64_t n_chunks, uint32_t want, uint64_t capacity
 }
 
 // The automatic (k, J) of a run that takes the one-lane or two-lane chunk forms with k_today items per chunk
-// (runtime.cpp miller_k_auto): below 65,536 items, or with miller_k set (explicit), (k_today, 1).  Otherwise k is the
+// (run_plan.hpp miller_k_auto): below 65,536 items, or with miller_k set (explicit), (k_today, 1).  Otherwise k is the
 // largest of 8, 4 for which some J <= k gives n_chunks J >= 65,536 lanes, and J the smallest such.  A pair is allowed
 // only if its n_chunks J slots fit capacity (the slots of f_chunk; ragged last chunks make n_chunks more than n / k)
 // and its chunks are at least half full on average (a run of tiny groups gains nothing from k: it keeps today's
@@ -103,7 +103,7 @@ inline Plan plan_auto(uint32_t n_items, const uint32_t* group_len, size_t n_grou
   return {k_today, 1};
 }
 
-// A run of one-item chunks keeps every set's Miller value for the fallback (runtime.cpp keep_f); chunks of k > 1 give
+// A run of one-item chunks keeps every set's Miller value for the fallback (run_plan.hpp keep_f); chunks of k > 1 give
 // that up, and a failed group's jobs re-run their Miller loops.  By op_counts.json the plan saves
 // 4,348 x 1.12 - 2,740 = ~2,100 products per set (two-lane k = 1 against k = 8) and a re-run costs ~4,900, so the plan
 // pays while fewer than ~0.43 of the sets sit in failing groups; a run holds on to one-item chunks from half that on:

@@ -1,6 +1,7 @@
-// Host types the two translation units of the runtime share: runtime.cpp (the asynchronous verification pipeline) and
-// helpers.cpp (the synchronous helper calls).  Nothing here is part of the C ABI (include/blsgpu.h): the namespace is
-// hidden, so none of it reaches the library's dynamic symbol table.
+// Host types the translation units of the runtime share: runtime.cpp (calls, sharding, dispatchers, options, the ABI),
+// pipeline.cpp (one pipeline run: run_call_shard) and helpers.cpp (the synchronous helper calls).  Nothing here is
+// part of the C ABI (include/blsgpu.h): the namespace is hidden, so none of it reaches the library's dynamic symbol
+// table.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +21,7 @@
 #include "../../include/blsgpu.h"
 #include "batch_rand.hpp"
 #include "kernels.h"
+#include "run_plan.hpp"  // Options, Shard, MsgIndex, al256 and the plan of a pipeline run: the HIP-free side
 
 namespace blsgpu_rt __attribute__((visibility("hidden"))) {
 
@@ -35,14 +37,21 @@ struct HipError {
 // g_grow_mu and tl_async_grow (below) are C++17 inline variables: DevBuf, defined in this header, needs them, and an
 // inline variable is ONE object in the library (one per thread for the thread-local) however many translation units
 // include the header.  In an anonymous namespace, or static, each unit would get its own: two copies of g_grow_mu
-// would undo what it is for, growth of stream-ordered buffers serialized across all threads.  The
-// runtime's other process-wide switches (g_fail_run_skip / g_fail_run_count, tl_dispatcher) are used by runtime.cpp
-// alone and are defined there.
+// would undo what it is for, growth of stream-ordered buffers serialized across all threads.  So are
+// the state runtime.cpp sets and pipeline.cpp reads (below); tl_dispatcher is used by runtime.cpp alone and is defined
+// there.
+// Device-failure injection (blsgpu_debug_inject, tests only): the next `count` pipeline runs after `skip` more fail as
+// if a HIP call had failed once their batch pass completed.
+inline std::atomic<int64_t> g_fail_run_skip{0}, g_fail_run_count{0};
+// per dispatcher thread: when the slot picked its run, and the milliseconds it spent merging calls into it (st.host_ms,
+// BLSGPU_HOST_TRACE)
+inline thread_local std::chrono::steady_clock::time_point tl_run_t0;
+inline thread_local double tl_merge_ms = 0;
 // Device buffer that only grows.  A slot's buffers grow stream-ordered (hipFreeAsync / hipMallocAsync on the
 // slot's stream): a plain hipFree waits for the whole device, so a merged run larger than any before would stall
 // every other slot's work (seen as 1.4-2.5 s call latencies in the bench's tail).  Growth doubles.
-// growths of stream-ordered slot buffers by this thread (run_shard: an input copy may leave the run's stream only when
-// no buffer of the run was (re)allocated in that stream's order)
+// growths of stream-ordered slot buffers by this thread (pipeline.cpp enqueue_batch_pass: an input copy may leave the
+// run's stream only when no buffer of the run was (re)allocated in that stream's order)
 inline thread_local uint64_t tl_async_grow = 0;
 // Diagnostics (BLSGPU_POISON=1 in the environment): every (re)allocated device buffer is filled with 0xA5 bytes before
 // first use, so a kernel that reads memory no kernel of its run wrote fails every time instead of only when the
@@ -75,7 +84,8 @@ inline bool grow_unlocked() {
   }();
   return on;
 }
-// Diagnostics (BLSGPU_FB_VERIFY=1): every fallback of small jobs is re-computed and compared (run_shard)
+// Diagnostics (BLSGPU_FB_VERIFY=1): every fallback of small jobs is re-computed and compared (pipeline.cpp
+// verify_fallback)
 inline bool fb_verify() {
   static const bool on = [] {
     const char* v = getenv("BLSGPU_FB_VERIFY");
@@ -112,8 +122,9 @@ struct DevBuf {
     } else if (st) {
       // the outgrown block is kept until the buffer is released instead of going back to the stream-ordered pool at
       // once (BLSGPU_GROW_FREE=1: freed at once, as before): with the adaptive group sizes, whose buffer shapes change
-      // over a fresh process's first runs, the kept per-set Miller values (run_shard keep_f) were found overwritten in
-      // ~6% of fresh C5 processes.  Growth doubles, so the kept blocks add up to less than the buffer.
+      // over a fresh process's first runs, the kept per-set Miller values (run_plan.hpp Forms::keep_f) were found
+      // overwritten in ~6% of fresh C5 processes.  Growth doubles, so the kept blocks add up to less
+      // than the buffer.
       if (p && grow_free()) HIPCHK(hipFreeAsync(p, st));
       else if (p) retired.push_back(p);
       p = nullptr;
@@ -165,9 +176,7 @@ struct HostBuf {  // pinned staging
 };
 
 constexpr int kStages = 8;
-constexpr size_t kMillerLineWords = (size_t)MILLER_STEPS * W_LINE;
-
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+static_assert(kMillerLineWords == (size_t)MILLER_STEPS * W_LINE, "run_plan.hpp");
 
 // One runtime slot: a dispatcher's staging and work buffers and its events.  The pipeline streams belong to the device
 // (Device::st) and are shared by its slots; each slot adds its own fallback stream (Slot::fb).  Under HIP's default of
@@ -182,7 +191,7 @@ struct Slot {
   // group verdicts (one D2H transfer).
   DevBuf<uint8_t> d_in, d_res, d_bytes, d_ok, d_fbflags;
   DevBuf<uint32_t> d_work, d_lines, d_S, d_F, d_G, d_list, d_msmB, d_msmW, d_fb;
-  DevBuf<uint32_t> d_fkeep;  // the batch pass's per-set Miller values, kept for the fallback (run_shard keep_f)
+  DevBuf<uint32_t> d_fkeep;  // the batch pass's per-set Miller values, kept for the fallback (run_plan.hpp Forms::keep_f)
   DevBuf<uint32_t> d_fseg;   // step segments: the (segment, group) heads of the F tree before their fold (k_f_fold)
   HostBuf<uint8_t> h_in, h_res, h_ok;
   HostBuf<uint32_t> h_list;
@@ -215,7 +224,8 @@ struct Task {
   uint32_t shard;
 };
 
-// The device's pipeline streams, shared by its slots: one per branch of a run's DAG (run_shard).  Runs of different
+// The device's pipeline streams, shared by its slots: one per branch of a run's DAG (pipeline.cpp
+// enqueue_batch_pass).  Runs of different
 // slots queue behind each other per branch, so the chip always has the next run's work while one run's tail drains.
 enum { kSig = 0, kMsg = 1, kPk = 2, kTail = 3, kStreams = 4, kMaxPairs = 3 };
 // streams created with the device's highest priority (bit k = stream k); see blsgpu_init
@@ -278,107 +288,6 @@ struct Device {
   double fail_rate = 0;  // EWMA over this device's runs of the fraction of invalid sets (group_adapt)
 };
 
-struct Options {  // snapshot taken at the start of each call
-  int64_t group_sets = 1024;
-  int64_t max_devices = 64;
-  bool profile = false;
-  bool dedupe = true;
-  int64_t miller_k = 0;  // pairings per Miller accumulator (shared squarings); 0 = by run size (miller_k_auto)
-  int64_t merge_sets = 131072;  // queued calls a slot merges into one pipeline run (sets), 0 = never
-  int64_t merge_wait_us = 2000;  // while runs are in flight, a slot waits this long for more calls to merge
-  int64_t idle_wait_us = 0;  // on an idle device, a slot waits up to this long while calls keep arriving (bursts)
-  int64_t pipeline_depth = 3;    // runs a device has in flight (taken by a slot, batch pass not yet complete)
-  int64_t group_policy = 0;    // 0 = groups of >= group_sets sets; 1 = the reference pool's jobs / requests / chunks
-  bool serial = false;  // diagnostics: every branch of a run on one stream (each kernel alone on the chip)
-  int64_t miller_segments = 0;  // diagnostics (BLSGPU_MILLER_SEGMENTS, read by blsgpu_init; no option key): step
-                                // segments of the one-lane accumulation, 0 = by run size (miller_plan.hpp plan_auto)
-  int64_t miller_lanes = 0;  // lanes per pairing of the one-item-chunk Miller accumulation: 0 = by run size, 1, 2
-  int64_t f_run_max = 16;    // merged runs: longest lane-serial run of the F product tree before the cooperative pairs
-  int64_t lane_tail_min = 0;  // runs of >= this many sets take the lane forms of the Horner passes and the groups'
-                                  // MillerLoop(-g1, S) (0 = never)
-  int64_t lane_tail_parts = 3;    // bit 0: Horner passes, bit 1: MillerLoop(-g1, S)
-  int64_t msm_slice_mid = 32;     // MSM slice length of runs of 1k-32k sets
-  int64_t lines_lanes = 2;        // lanes per message of the Miller lines (1, or 2 = lane pairs: fp2x.hpp)
-  int64_t merge_balance = 0;      // a backlog above merge_sets is cut into equal runs
-  int64_t early_release = 0;      // a run leaves the pipeline count when its message branch is done
-  int64_t tail_on_msg = 0;        // the group stage runs on the pair's high-priority message stream
-  int64_t copy_stream = 0;        // a run's input copy on the table stream (not behind the pair's previous tail)
-  int64_t msm_tree = 1;           // those runs sum each range's slices by a pairwise tree
-  int64_t coop_max = 512;         // runs of <= this many pairings take the cooperative Miller loops (k_miller_coop)
-  int64_t coop_g2_max = 4096;     // runs of <= this many sets take the cooperative [|z|] chains (clearing, subgroup)
-  int64_t coop_excl_max = 512;    // cooperative workgroups take a CU each only in runs of <= this many items
-  int64_t rsig_spec = 1;          // small idle runs form every r_i sig_i beside the batch pass (for the fallback)
-  int64_t spec_large = 1;         // runs above small_max on an idle device take the speculative MSM too
-  int64_t spec_gsm = 0;           // a speculative run's MillerLoop(-g1, S) follows its MSM on the other pair's stream
-  int64_t fb_lane_min = 256;      // fallback check launches of >= this many checks take one lane per check (0 = never)
-  int64_t route_split_sets = 16384;  // a call is split over min(devices, sets / this) devices, else routed whole
-  int64_t acc6_max = 16384;       // one-item-chunk runs of <= this many chunks take the six-lane accumulation
-  int64_t miller_pairs = 0;       // larger runs: the lane-pair accumulation (k_miller_accx, two waves per SIMD)
-  int64_t small_max = 4096;       // runs of <= this many sets are latency-first (speculation, cooperative fallback checks)
-  int64_t fb_direct_min = 1024;   // large runs under load with >= this many retried jobs check each directly (0 = never)
-  int64_t fb_check6 = 2;          // those runs' lane checks: 0 one lane per check; 1 MillerLoop(-g1, S) one lane and the
-                                  // final exponentiation six lanes per check (gt6.hpp); 2 both on six lanes
-  int64_t keep_f = 1;             // the fallback reuses the batch pass's per-set Miller values (0: re-runs the loops)
-  int64_t keep_copy = 0;          // how they are copied aside: 0 hipMemcpyAsync, 1 a copy kernel on the same stream
-  int64_t fb_force_busy = 0;      // tests: every run's fallback takes the under-load forms
-  int64_t urgent_lane = 1;        // calls with a BLSGPU_JOB_URGENT job run on the device's urgent lane
-  int64_t urgent_max_sets = 512;  // larger urgent calls go to the head of the device queue instead
-  int64_t urgent_excl = 0;        // urgent runs may use the exclusive-CU padding of the cooperative kernels
-  int64_t urgent_wait_us = 300;   // the urgent dispatcher lingers this long for more urgent calls of a burst
-  int64_t group_adapt = 1;        // batch groups shrink below group_sets while the device sees invalid sets (DESIGN
-                                  // §5.2: safe once outgrown buffers stay allocated, DevBuf::ensure)
-  bool same_run(const struct Options& o) const {
-    return group_sets == o.group_sets && profile == o.profile && dedupe == o.dedupe && miller_k == o.miller_k &&
-           group_policy == o.group_policy && serial == o.serial && miller_lanes == o.miller_lanes && miller_segments == o.miller_segments &&
-           f_run_max == o.f_run_max && lane_tail_min == o.lane_tail_min &&
-           lane_tail_parts == o.lane_tail_parts &&
-           msm_slice_mid == o.msm_slice_mid && msm_tree == o.msm_tree &&
-           lines_lanes == o.lines_lanes && merge_balance == o.merge_balance && early_release == o.early_release && tail_on_msg == o.tail_on_msg && copy_stream == o.copy_stream && coop_max == o.coop_max &&
-           coop_g2_max == o.coop_g2_max && coop_excl_max == o.coop_excl_max && rsig_spec == o.rsig_spec && spec_large == o.spec_large && spec_gsm == o.spec_gsm &&
-           fb_lane_min == o.fb_lane_min && acc6_max == o.acc6_max && miller_pairs == o.miller_pairs && small_max == o.small_max &&
-           fb_direct_min == o.fb_direct_min && fb_check6 == o.fb_check6 && fb_force_busy == o.fb_force_busy &&
-           group_adapt == o.group_adapt && keep_f == o.keep_f && keep_copy == o.keep_copy;
-  }
-};
-
-// ---- message deduplication: open addressing on the 32-byte signing roots ----------------------------------
-struct MsgIndex {
-  std::vector<uint32_t> slot;  // 1 + unique index, 0 = empty
-  uint64_t key;
-  explicit MsgIndex(uint32_t n, uint64_t k) : key(k) {
-    size_t cap = 16;
-    while (cap < (size_t)n * 2) cap <<= 1;
-    slot.assign(cap, 0);
-  }
-  static uint64_t mix(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-  }
-  size_t hash(const uint8_t* msgs, uint32_t i) const {
-    uint64_t w[4];
-    memcpy(w, msgs + (size_t)i * 32, 32);
-    return (size_t)(mix(w[0] ^ key) ^ mix(w[1] + key) ^ w[2] ^ (w[3] << 1)) & (slot.size() - 1);
-  }
-  // returns the unique index of msg; appends to `uniq` (set indices of first occurrences) when new
-  uint32_t find_or_add(const uint8_t* msgs, uint32_t i, std::vector<uint32_t>& uniq) {
-    return find_or_add_h(msgs, i, hash(msgs, i), uniq);
-  }
-  uint32_t find_or_add_h(const uint8_t* msgs, uint32_t i, size_t h, std::vector<uint32_t>& uniq) {
-    const size_t mask = slot.size() - 1;
-    for (;;) {
-      const uint32_t s = slot[h];
-      if (!s) {
-        uniq.push_back(i);
-        slot[h] = (uint32_t)uniq.size();
-        return (uint32_t)uniq.size() - 1;
-      }
-      if (memcmp(msgs + (size_t)uniq[s - 1] * 32, msgs + (size_t)i * 32, 32) == 0) return s - 1;
-      h = (h + 1) & mask;
-    }
-  }
-};
-
 inline double ms_since(std::chrono::steady_clock::time_point t) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
@@ -386,6 +295,15 @@ inline double ms_since(std::chrono::steady_clock::time_point t) {
 // The call's scalar key and message-index hash key from its seed (batch_rand.hpp): seed 0 = 256 bits of OS
 // entropy, else the comparison-run key of the seed.  false = no entropy: the call must fail (never a constant).
 bool resolve_key(uint64_t seed, batch_rand::Key& key, uint64_t& hash_key);  // runtime.cpp
+
+// pubkey mode of a batch: 0 table, 1 one key per set (bytes), 2 bytes aggregate
+inline int pk_mode(const blsgpu_batch& b) { return !b.pk_bytes ? 0 : (b.set_pk_first ? 2 : 1); }
+
+// pipeline.cpp: one shard of a call (or a merged batch) as one pipeline run on a slot, under the call's group policy
+// (writes job_result[job_begin .. job_end)); and the run's leaving the device's in-flight count (once)
+int run_call_shard(Device& d, Slot& sl, const blsgpu_batch& b, const Shard& sh, int8_t* job_result, uint64_t seed,
+                   const Options& opt, uint32_t max_index, blsgpu_stats& st, const uint64_t* scal_words);
+void release_inflight(Device& d, Slot& sl);
 
 }  // namespace blsgpu_rt
 

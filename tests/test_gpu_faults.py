@@ -1,7 +1,7 @@
 """GPU tests of the failure paths: the speculative small-run MSM's exactness, fail-closed batch scalars, injected
 device failures, and the in-process two-shard path at C4's full size.
 
-* Speculative MSM (runtime.cpp run_shard, `spec`): an idle small run sums every DECODED signature into S_g before
+* Speculative MSM (run_plan.hpp `Forms::spec`, pipeline.cpp enqueue_batch_pass and classify_groups): an idle small run sums every DECODED signature into S_g before
   the job mask exists, so a group holding a rejected job (a signature outside G2, a bad pubkey) is not the equation
   of its clean jobs; those must be re-checked with exact masks.  Cases: a 2-job call with one such job and one valid
   job -> [-code, 1] (the advisor's counterexample), and an idle 128-set call mixing a non-G2 signature, a

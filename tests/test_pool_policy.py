@@ -1,6 +1,6 @@
 """The reference pool's chunking rule (A5), CPU only: chunkifyMaximizeChunkSize against the reference's own test
 table (packages/beacon-node/test/unit/chain/bls/utils.test.ts:7-25, minPerChunk 3 over linspace(0, i)), through the
-oracle's restatement (oracle/blscpu.c) and the product's (runtime.cpp, C-ABI blsgpu_chunkify) -- the rule
+oracle's restatement (oracle/blscpu.c) and the product's (run_plan.hpp chunk_size, C-ABI blsgpu_chunkify) -- the rule
 group_policy 1 applies to calls (128 sets, multithread/index.ts:156) and to a request's batchable jobs (16,
 multithread/worker.ts:17,56)."""
 import pytest
