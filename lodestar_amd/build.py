@@ -78,7 +78,8 @@ def _tu_deps(src):
     declarations and the runtime's own headers; a kernel TU sees every arithmetic header."""
     if src.endswith(".cpp"):
         return [os.path.join(CSRC, f) for f in (src, "kernels.h", "batch_rand.hpp", "runtime_internal.hpp",
-                                                "run_plan.hpp", "helper_layout.hpp", "miller_plan.hpp")] + [
+                                                "run_plan.hpp", "options.hpp", "call_plan.hpp", "helper_layout.hpp",
+                                                "miller_plan.hpp")] + [
             os.path.join(ROOT, "include", "blsgpu.h")]
     return [os.path.join(CSRC, src)] + _headers()
 

@@ -1,4 +1,4 @@
-// Batch scalars of the random linear combination (host side, runtime.cpp).
+// Batch scalars of the random linear combination (host side: call_plan.hpp shard_scalars, runtime.cpp resolve_key).
 //
 // The reference draws blst's 64-bit scalars from fresh randomness in every verifyMultipleAggregateSignatures call
 // (chain/bls/maybeBatch.ts:17-26 -> blst; SURVEY.md §7 hard part 5): an attacker who could predict them could build
@@ -102,7 +102,7 @@ inline Key seed_key(uint64_t seed) {
               0x2072616cu, 0x7379656bu}};
 }
 
-// The message index's hash key (runtime_internal.hpp MsgIndex): 64 bits of the call key's own keystream under a separate nonce,
+// The message index's hash key (run_plan.hpp MsgIndex): 64 bits of the call key's own keystream under a separate nonce,
 // so no key word of the scalars' keystream ever drives the host hash table (a timing leak of the table would reveal
 // nothing about the scalars).
 inline uint64_t hash_key(const Key& key) {

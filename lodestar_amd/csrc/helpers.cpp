@@ -265,7 +265,7 @@ uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets) { return awr_lanes
 
 // ---- one-call same-message verification ------------------------------------------------------------------------
 // A phase of at most kSameCoopMax pairings takes the cooperative kernels (a workgroup per Miller loop and per check:
-// latency), a larger one the lane forms (throughput).  512 is option "coop_max"'s default, taken as a constant: the
+// latency), a larger one the lane forms (throughput).  512 is the coop_max option's default, taken as a constant: the
 // helper calls read no option.
 constexpr uint32_t kSameCoopMax = 512;
 uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags) {

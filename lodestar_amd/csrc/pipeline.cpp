@@ -1,7 +1,7 @@
 // The run path of libblsgpu: one device's shard of a call (or of a merged batch) as one pipeline run.  run_shard is a
 // short sequence of phases: the run's plan (run_plan.hpp, plain arithmetic, tested without a GPU), the staging of its
 // inputs, the stream DAG of its batch pass, the sorting of the group verdicts, the fallback of failed groups' jobs.
-// runtime.cpp (calls, sharding, dispatchers, options, the ABI) enters through run_call_shard.
+// runtime.cpp (calls, dispatchers, the ABI) enters through run_call_shard.
 #include <stdio.h>
 
 #include "runtime_internal.hpp"

@@ -16,10 +16,7 @@
 #include "../../include/blsgpu.h"
 #include "helper_layout.hpp"
 #include "miller_plan.hpp"
-
-#ifndef MSM_SLICE  // sets per MSM slice (kernels.h has the same guarded default; a build may override both with -D)
-#define MSM_SLICE 256
-#endif
+#include "options.hpp"  // Options (the snapshot a call takes) and MSM_SLICE
 
 namespace blsgpu_rt __attribute__((visibility("hidden"))) {
 
@@ -37,69 +34,6 @@ constexpr size_t kMsmBucketWords = 128 * kG2J, kMsmWindowWords = 16 * kG2J;
 
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-struct Options {  // snapshot taken at the start of each call
-  int64_t group_sets = 1024;
-  int64_t max_devices = 64;
-  bool profile = false;
-  bool dedupe = true;
-  int64_t miller_k = 0;  // pairings per Miller accumulator (shared squarings); 0 = by run size (miller_k_auto)
-  int64_t merge_sets = 131072;  // queued calls a slot merges into one pipeline run (sets), 0 = never
-  int64_t merge_wait_us = 2000;  // while runs are in flight, a slot waits this long for more calls to merge
-  int64_t idle_wait_us = 0;  // on an idle device, a slot waits up to this long while calls keep arriving (bursts)
-  int64_t pipeline_depth = 3;    // runs a device has in flight (taken by a slot, batch pass not yet complete)
-  int64_t group_policy = 0;    // 0 = groups of >= group_sets sets; 1 = the reference pool's jobs / requests / chunks
-  bool serial = false;  // diagnostics: every branch of a run on one stream (each kernel alone on the chip)
-  int64_t miller_segments = 0;  // diagnostics (BLSGPU_MILLER_SEGMENTS, read by blsgpu_init; no option key): step
-                                // segments of the one-lane accumulation, 0 = by run size (miller_plan.hpp plan_auto)
-  int64_t miller_lanes = 0;  // lanes per pairing of the one-item-chunk Miller accumulation: 0 = by run size, 1, 2
-  int64_t f_run_max = 16;    // merged runs: longest lane-serial run of the F product tree before the cooperative pairs
-  int64_t lane_tail_min = 0;  // runs of >= this many sets take the lane forms of the Horner passes and the groups'
-                                  // MillerLoop(-g1, S) (0 = never)
-  int64_t lane_tail_parts = 3;    // bit 0: Horner passes, bit 1: MillerLoop(-g1, S)
-  int64_t msm_slice_mid = 32;     // MSM slice length of runs of 1k-32k sets
-  int64_t lines_lanes = 2;        // lanes per message of the Miller lines (1, or 2 = lane pairs: fp2x.hpp)
-  int64_t merge_balance = 0;      // a backlog above merge_sets is cut into equal runs
-  int64_t early_release = 0;      // a run leaves the pipeline count when its message branch is done
-  int64_t tail_on_msg = 0;        // the group stage runs on the pair's high-priority message stream
-  int64_t copy_stream = 0;        // a run's input copy on the table stream (not behind the pair's previous tail)
-  int64_t msm_tree = 1;           // those runs sum each range's slices by a pairwise tree
-  int64_t coop_max = 512;         // runs of <= this many pairings take the cooperative Miller loops (k_miller_coop)
-  int64_t coop_g2_max = 4096;     // runs of <= this many sets take the cooperative [|z|] chains (clearing, subgroup)
-  int64_t coop_excl_max = 512;    // cooperative workgroups take a CU each only in runs of <= this many items
-  int64_t rsig_spec = 1;          // small idle runs form every r_i sig_i beside the batch pass (for the fallback)
-  int64_t spec_large = 1;         // runs above small_max on an idle device take the speculative MSM too
-  int64_t spec_gsm = 0;           // a speculative run's MillerLoop(-g1, S) follows its MSM on the other pair's stream
-  int64_t fb_lane_min = 256;      // fallback check launches of >= this many checks take one lane per check (0 = never)
-  int64_t route_split_sets = 16384;  // a call is split over min(devices, sets / this) devices, else routed whole
-  int64_t acc6_max = 16384;       // one-item-chunk runs of <= this many chunks take the six-lane accumulation
-  int64_t miller_pairs = 0;       // larger runs: the lane-pair accumulation (k_miller_accx, two waves per SIMD)
-  int64_t small_max = 4096;       // runs of <= this many sets are latency-first (speculation, cooperative fallback checks)
-  int64_t fb_direct_min = 1024;   // large runs under load with >= this many retried jobs check each directly (0 = never)
-  int64_t fb_check6 = 2;          // those runs' lane checks: 0 one lane per check; 1 MillerLoop(-g1, S) one lane and the
-                                  // final exponentiation six lanes per check (gt6.hpp); 2 both on six lanes
-  int64_t keep_f = 1;             // the fallback reuses the batch pass's per-set Miller values (0: re-runs the loops)
-  int64_t keep_copy = 0;          // how they are copied aside: 0 hipMemcpyAsync, 1 a copy kernel on the same stream
-  int64_t fb_force_busy = 0;      // tests: every run's fallback takes the under-load forms
-  int64_t urgent_lane = 1;        // calls with a BLSGPU_JOB_URGENT job run on the device's urgent lane
-  int64_t urgent_max_sets = 512;  // larger urgent calls go to the head of the device queue instead
-  int64_t urgent_excl = 0;        // urgent runs may use the exclusive-CU padding of the cooperative kernels
-  int64_t urgent_wait_us = 300;   // the urgent dispatcher lingers this long for more urgent calls of a burst
-  int64_t group_adapt = 1;        // batch groups shrink below group_sets while the device sees invalid sets (DESIGN
-                                  // §5.2: safe once outgrown buffers stay allocated, DevBuf::ensure)
-  bool same_run(const struct Options& o) const {
-    return group_sets == o.group_sets && profile == o.profile && dedupe == o.dedupe && miller_k == o.miller_k &&
-           group_policy == o.group_policy && serial == o.serial && miller_lanes == o.miller_lanes && miller_segments == o.miller_segments &&
-           f_run_max == o.f_run_max && lane_tail_min == o.lane_tail_min &&
-           lane_tail_parts == o.lane_tail_parts &&
-           msm_slice_mid == o.msm_slice_mid && msm_tree == o.msm_tree &&
-           lines_lanes == o.lines_lanes && merge_balance == o.merge_balance && early_release == o.early_release && tail_on_msg == o.tail_on_msg && copy_stream == o.copy_stream && coop_max == o.coop_max &&
-           coop_g2_max == o.coop_g2_max && coop_excl_max == o.coop_excl_max && rsig_spec == o.rsig_spec && spec_large == o.spec_large && spec_gsm == o.spec_gsm &&
-           fb_lane_min == o.fb_lane_min && acc6_max == o.acc6_max && miller_pairs == o.miller_pairs && small_max == o.small_max &&
-           fb_direct_min == o.fb_direct_min && fb_check6 == o.fb_check6 && fb_force_busy == o.fb_force_busy &&
-           group_adapt == o.group_adapt && keep_f == o.keep_f && keep_copy == o.keep_copy;
-  }
-};
-
 // One device's part of a call: contiguous jobs and their sets.
 struct Shard {
   uint32_t job_begin, job_end;  // job range
@@ -107,6 +41,9 @@ struct Shard {
   uint32_t dev = 0;             // device index (routing)
   int64_t cost = 0;             // routing cost, x256 (Device::load)
 };
+
+// pubkey mode of a batch: 0 table, 1 one key per set (bytes), 2 bytes aggregate
+inline int pk_mode(const blsgpu_batch& b) { return !b.pk_bytes ? 0 : (b.set_pk_first ? 2 : 1); }
 
 // ---- message deduplication: open addressing on the 32-byte signing roots ----------------------------------
 struct MsgIndex {

@@ -18,20 +18,26 @@
 //     group on its own (the reference re-verifies each job of a failed chunk, worker.ts:76-98): per job the
 //     answer is the reference's, valid iff every set of the job verifies.
 // There is no CPU verification path: without a usable GPU blsgpu_init fails.
+//
+// This unit holds the contexts, devices, slots, the two dispatchers (worker_loop, urgent_loop) with the one function
+// that runs and completes the parts they form (run_parts), the uploads and the ABI entry points.  The host arithmetic
+// lives in headers with no HIP in them, each checked by CPU tests through a probe: what a call decides before a run
+// and the packing of a merged run in call_plan.hpp, the options table in options.hpp, the plan of a run in
+// run_plan.hpp (pipeline.cpp runs it); helpers.cpp holds the synchronous helper calls.
 #include <pthread.h>
 #include <stdio.h>
 #include <sys/random.h>
 
-#include <string>
 #include <system_error>
 
+#include "call_plan.hpp"  // the HIP-free side of a call: validity, sharding, routing, scalars, merged batches
 #include "runtime_internal.hpp"
 
 using namespace blsgpu_rt;
 
 namespace {
 
-// set on the runtime's dispatcher threads (a "slots" change from a done callback would join its own thread)
+// set on the runtime's dispatcher threads (a `slots` change from a done callback would join its own thread)
 thread_local bool tl_dispatcher = false;
 
 }  // namespace
@@ -72,85 +78,6 @@ struct Call {
 }  // namespace blsgpu_rt
 
 namespace {
-
-// ---- contiguous cost-balanced sharding (the rule lodestar_amd/shard.py restates) ------------------------
-// cost of a job = its sets + 1/256 per aggregated pubkey; part k ends at the largest job boundary whose
-// prefix cost is <= total (k+1)/n_parts; the last part takes the rest.
-void shard_rule(const uint32_t* jfs, const uint32_t* spf, uint32_t n_jobs, uint32_t n_parts, uint32_t* out) {
-  const uint32_t n_sets = n_jobs ? jfs[n_jobs] : 0;
-  std::vector<double> set_prefix(n_sets + 1, 0.0);
-  for (uint32_t i = 0; i < n_sets; i++)
-    set_prefix[i + 1] = set_prefix[i] + 1.0 + (spf ? (double)(spf[i + 1] - spf[i]) / 256.0 : 0.0);
-  std::vector<double> cost(n_jobs + 1);
-  for (uint32_t j = 0; j <= n_jobs; j++) cost[j] = set_prefix[n_jobs ? jfs[j] : 0];
-  uint32_t j0 = 0;
-  out[0] = 0;
-  for (uint32_t k = 0; k < n_parts; k++) {
-    uint32_t j1;
-    if (k + 1 == n_parts) {
-      j1 = n_jobs;
-    } else {
-      const double target = cost[n_jobs] * (k + 1) / n_parts;
-      // largest j1 >= j0 with cost[j1] <= target
-      j1 = (uint32_t)(std::upper_bound(cost.begin(), cost.end(), target) - cost.begin());
-      j1 = j1 ? j1 - 1 : 0;
-      j1 = std::max(j0, j1);
-    }
-    out[k + 1] = j1;
-    j0 = j1;
-  }
-}
-
-// ---- routing calls over devices (the rule lodestar_amd/shard.py route_call restates) ---------------------------
-// A call is split over k = min(devices, max(1, n_sets / split_sets)) devices and otherwise routed WHOLE: a gossip
-// call (<= 16k sets at the default) runs on one device at the latency of its full size instead of becoming 2k-set
-// shards on 8 devices (mid-size runs, each no faster than the whole call), while an epoch-scale call (C4: 32,768 sets)
-// still splits.  The k devices are the least loaded (queued + running cost); ties go by distance from the rotating
-// `start`, so equal loads spread.  out[0 .. k) = device indices in shard order; returns k.
-uint32_t route_rule(uint32_t n_sets, uint32_t n_dev, const int64_t* load, int64_t split_sets, uint32_t start,
-                    uint32_t* out) {
-  if (n_dev == 0) return 0;
-  const uint64_t per = (uint64_t)std::max<int64_t>(1, split_sets);
-  const uint32_t k = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_dev, n_sets / per));
-  std::vector<uint32_t> order(n_dev);
-  for (uint32_t d = 0; d < n_dev; d++) order[d] = d;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    if (load[a] != load[b]) return load[a] < load[b];
-    return (a + n_dev - start % n_dev) % n_dev < (b + n_dev - start % n_dev) % n_dev;
-  });
-  std::sort(order.begin(), order.begin() + k);  // shard order = device order (contiguous job ranges)
-  for (uint32_t i = 0; i < k; i++) out[i] = order[i];
-  return k;
-}
-
-
-uint32_t max_table_index(const blsgpu_batch* b) {
-  uint32_t m = 0;
-  if (!b->pk_bytes && b->n_sets)
-    for (uint32_t k = 0; k < b->set_pk_first[b->n_sets]; k++) m = std::max(m, b->pk_index[k]);
-  return m;
-}
-
-int validate_batch(const blsgpu_batch* b) {
-  if (!b || !b->job_first_set) return BLSGPU_ERR_ARGS;
-  if (b->n_jobs == 0) return b->n_sets == 0 ? BLSGPU_OK : BLSGPU_ERR_ARGS;
-  if (b->job_first_set[0] != 0 || b->job_first_set[b->n_jobs] != b->n_sets) return BLSGPU_ERR_ARGS;
-  for (uint32_t j = 0; j < b->n_jobs; j++)
-    if (b->job_first_set[j + 1] < b->job_first_set[j]) return BLSGPU_ERR_ARGS;
-  if (b->n_sets == 0) return BLSGPU_OK;
-  if (!b->msgs || !b->sigs || !b->sig_len) return BLSGPU_ERR_ARGS;
-  if (b->sig_stride < 96) return BLSGPU_ERR_ARGS;
-  for (uint32_t i = 0; i < b->n_sets; i++)
-    if (b->sig_len[i] > b->sig_stride && (b->sig_len[i] == 96 || b->sig_len[i] == 192)) return BLSGPU_ERR_ARGS;
-  if (!b->pk_bytes && (!b->set_pk_first || !b->pk_index)) return BLSGPU_ERR_ARGS;
-  if (b->set_pk_first) {
-    if (b->set_pk_first[0] != 0) return BLSGPU_ERR_ARGS;
-    for (uint32_t i = 0; i < b->n_sets; i++)
-      if (b->set_pk_first[i + 1] < b->set_pk_first[i]) return BLSGPU_ERR_ARGS;
-  }
-  return BLSGPU_OK;
-}
-
 
 void finish_call(Call* c) {
   blsgpu_stats local{};
@@ -195,176 +122,55 @@ void finish_call(Call* c) {
   leave(ctx);
 }
 
-// Batch scalar words of a shard (shard-relative): single-set non-batchable jobs use r = 1 (word 0, CoreVerify,
-// maybeBatch.ts:34-38), every other set i the call's keystream word i (batch_rand.hpp).
-void shard_scalars(const blsgpu_batch& b, const Shard& sh, const batch_rand::Key& key, uint64_t* out) {
-  if (sh.set_end > sh.set_begin) batch_rand::words(key, sh.set_begin, sh.set_end - sh.set_begin, out);
-  for (uint32_t j = sh.job_begin; j < sh.job_end; j++) {
-    const uint32_t a = b.job_first_set[j], e = b.job_first_set[j + 1];
-    const bool batchable = b.job_flags && (b.job_flags[j] & 1u);
-    if (!batchable && e - a == 1) out[a - sh.set_begin] = 0;
-  }
-}
-
 // Does the device's table hold every index the call's shard uses?  (Checked per device under its table lock: a
 // call may race an upload that has reached some devices only.)
 inline bool table_covers(const Device& d, const Call* c, const Shard& sh) {
-  const blsgpu_batch& b = c->b;
-  if (b.pk_bytes || !b.set_pk_first || sh.set_end == sh.set_begin) return true;
-  if (b.set_pk_first[sh.set_end] == b.set_pk_first[sh.set_begin]) return true;
-  return c->max_index < d.table_n;
+  return table_covers(c->b, sh, c->max_index, d.table_n);
 }
 
 // Several queued shards (of different calls) run as ONE pipeline: their inputs are concatenated into one
-// batch (jobs and results stay per call), so a launch fills the chip instead of one call's 16k-set share --
-// the device-side counterpart of the pool packing queued jobs into one worker request (prepareWork,
+// batch (call_plan.hpp MergedBatch; jobs and results stay per call), so a launch fills the chip instead of one call's
+// 16k-set share -- the device-side counterpart of the pool packing queued jobs into one worker request (prepareWork,
 // multithread/index.ts:386-401).  Jobs never interact, so every job's result is the one it gets alone.  A call
 // that cannot run (a table index beyond the device's table) is completed with ERR_ARGS on its own and never
-// joins the run; a failure of the run completes its calls with DEVICE_ERROR (every job rejected, never `false`).
+// joins the run; a failure of the run gives its calls DEVICE_ERROR.  rcs: the parts' status codes.
 // The caller holds the device's table lock (shared).
 void run_merged(Device& d, Slot& sl, const std::vector<Task>& parts, std::vector<int>& rcs) {
   const auto t_merge0 = std::chrono::steady_clock::now();
   std::vector<size_t> live;
+  std::vector<CallPart> live_parts;
+  uint32_t max_index = 0;
   for (size_t p = 0; p < parts.size(); p++) {
-    const Call* c = parts[p].call;
-    if (c->ctx->closed && !c->sync)
+    Call* c = parts[p].call;
+    const Shard& sh = c->shards[parts[p].shard];
+    if (c->ctx->closed && !c->sync) {
       rcs[p] = BLSGPU_ERR_CLOSED;
-    else if (!table_covers(d, c, c->shards[parts[p].shard]))
+    } else if (!table_covers(d, c, sh)) {
       rcs[p] = BLSGPU_ERR_ARGS;
-    else
+    } else {
       live.push_back(p);
+      live_parts.push_back({c->b, sh, c->key, c->job_result});
+      max_index = std::max(max_index, c->max_index);
+    }
   }
   if (live.empty()) return;
   int rc = BLSGPU_OK;
   blsgpu_stats st{};
-  std::vector<int8_t> res;
   try {
+    const MergedBatch m(live_parts);
+    std::vector<int8_t> res(std::max<uint32_t>(m.nj, 1), 0);
     const Call* c0 = parts[live[0]].call;
-    const int mode = pk_mode(c0->b);
-    uint32_t n = 0, nj = 0, npk = 0, max_index = 0;
-    for (size_t p : live) {
-      const Task& t = parts[p];
-      const Shard& sh = t.call->shards[t.shard];
-      const blsgpu_batch& b = t.call->b;
-      n += sh.set_end - sh.set_begin;
-      nj += sh.job_end - sh.job_begin;
-      if (b.set_pk_first) npk += b.set_pk_first[sh.set_end] - b.set_pk_first[sh.set_begin];
-      max_index = std::max(max_index, t.call->max_index);
-    }
-    // the parts' offsets (sets, jobs, pubkeys), then every part packed in parallel into its own ranges: the batch
-    // scalars (ChaCha20, ~0.4 ms per 16k-set call) and the copies of a 131k-set run took ~2.5 ms on one thread
-    uint32_t sig_w = 96;
-    std::vector<uint32_t> p_so, p_jo, p_ko;
-    {
-      uint32_t so = 0, jo = 0, ko = 0;
-      for (size_t p : live) {
-        const Task& t = parts[p];
-        const Shard& sh = t.call->shards[t.shard];
-        const blsgpu_batch& b = t.call->b;
-        p_so.push_back(so);
-        p_jo.push_back(jo);
-        p_ko.push_back(ko);
-        so += sh.set_end - sh.set_begin;
-        jo += sh.job_end - sh.job_begin;
-        if (b.set_pk_first) ko += b.set_pk_first[sh.set_end] - b.set_pk_first[sh.set_begin];
-        for (uint32_t i = sh.set_begin; i < sh.set_end && sig_w == 96; i++)
-          if (b.sig_len[i] == 192) sig_w = 192;
-      }
-    }
-    std::vector<uint32_t> jfs(nj + 1), siglen(n), spf(mode == 1 ? 1 : n + 1), pki(mode == 0 ? npk : 0);
-    std::vector<uint8_t> flags(nj), pkb(mode == 1 ? (size_t)n * 96 : mode == 2 ? (size_t)npk * 96 : 0),
-        msgs((size_t)n * 32), sigs((size_t)n * sig_w, 0);
-    std::vector<uint64_t> scal(std::max<uint32_t>(n, 1));
-    jfs[0] = 0;
-    spf[0] = 0;
-    auto pack = [&](size_t q) {
-      if (q) pthread_setname_np(pthread_self(), "blsgpu-pack");
-      const Task& t = parts[live[q]];
-      const Shard& sh = t.call->shards[t.shard];
-      const blsgpu_batch& b = t.call->b;
-      const uint32_t so = p_so[q], jo = p_jo[q], ko = p_ko[q], ns = sh.set_end - sh.set_begin;
-      shard_scalars(b, sh, t.call->key, scal.data() + so);
-      for (uint32_t j = sh.job_begin; j < sh.job_end; j++) {
-        jfs[jo + (j - sh.job_begin) + 1] = so + b.job_first_set[j + 1] - sh.set_begin;
-        flags[jo + (j - sh.job_begin)] = b.job_flags ? b.job_flags[j] : 0;
-      }
-      memcpy(siglen.data() + so, b.sig_len + sh.set_begin, (size_t)ns * 4);
-      if (b.sig_stride == sig_w) {
-        memcpy(sigs.data() + (size_t)so * sig_w, b.sigs + (size_t)sh.set_begin * sig_w, (size_t)ns * sig_w);
-      } else {
-        for (uint32_t i = sh.set_begin; i < sh.set_end; i++) {
-          const uint32_t len = b.sig_len[i];
-          if (len == 96 || len == 192)
-            memcpy(sigs.data() + (size_t)(so + i - sh.set_begin) * sig_w, b.sigs + (size_t)i * b.sig_stride, len);
-        }
-      }
-      memcpy(msgs.data() + (size_t)so * 32, b.msgs + (size_t)sh.set_begin * 32, (size_t)ns * 32);
-      if (mode == 1) {
-        memcpy(pkb.data() + (size_t)so * 96, b.pk_bytes + (size_t)sh.set_begin * 96, (size_t)ns * 96);
-      } else {
-        const uint32_t k0 = b.set_pk_first[sh.set_begin], k1 = b.set_pk_first[sh.set_end];
-        for (uint32_t i = sh.set_begin; i < sh.set_end; i++)
-          spf[so + (i - sh.set_begin) + 1] = ko + b.set_pk_first[i + 1] - k0;
-        if (mode == 0)
-          memcpy(pki.data() + ko, b.pk_index + k0, (size_t)(k1 - k0) * 4);
-        else
-          memcpy(pkb.data() + (size_t)ko * 96, b.pk_bytes + (size_t)k0 * 96, (size_t)(k1 - k0) * 96);
-      }
-    };
-    {  // parts of >= 4,096 sets on their own threads (a small part packs faster than a thread starts)
-      struct Joiner {  // joins the started threads on every exit, so none is destroyed while joinable
-        std::vector<std::thread> th;
-        ~Joiner() {
-          for (auto& x : th)
-            if (x.joinable()) x.join();
-        }
-      } j;
-      std::vector<uint8_t> inline_pack(live.size(), 0);
-      for (size_t q = 0; q < live.size(); q++) {
-        const Shard& sh = parts[live[q]].call->shards[parts[live[q]].shard];
-        inline_pack[q] = q == 0 || sh.set_end - sh.set_begin < 4096;
-        if (inline_pack[q]) continue;
-        try {
-          j.th.emplace_back(pack, q);
-        } catch (std::system_error&) {  // no thread: this part packs on the current one
-          inline_pack[q] = 1;
-        }
-      }
-      for (size_t q = 0; q < live.size(); q++)
-        if (inline_pack[q]) pack(q);
-    }
-    blsgpu_batch mb{};
-    mb.n_sets = n;
-    mb.n_jobs = nj;
-    mb.job_first_set = jfs.data();
-    mb.job_flags = flags.data();
-    mb.pk_bytes = mode ? pkb.data() : nullptr;
-    mb.set_pk_first = mode == 1 ? nullptr : spf.data();
-    mb.pk_index = mode == 0 ? pki.data() : nullptr;
-    mb.msgs = msgs.data();
-    mb.sigs = sigs.data();
-    mb.sig_len = siglen.data();
-    mb.sig_stride = sig_w;
-    res.assign(std::max<uint32_t>(nj, 1), 0);
-    const Shard all{0, nj, 0, n};
     tl_merge_ms = ms_since(t_merge0);
-    rc = run_call_shard(d, sl, mb, all, res.data(), c0->seed, c0->opt, max_index, st, scal.data());
+    rc = run_call_shard(d, sl, m.b, Shard{0, m.nj, 0, m.n}, res.data(), c0->seed, c0->opt, max_index, st,
+                        m.scal.data());
+    if (rc == BLSGPU_OK) scatter_results(m, live_parts, res.data());
   } catch (...) {
     rc = BLSGPU_DEVICE_ERROR;
   }
   st.run_calls = (uint32_t)live.size();
-  uint32_t jo = 0;
   for (size_t k = 0; k < live.size(); k++) {
     const size_t p = live[k];
-    Call* c = parts[p].call;
-    const Shard& sh = c->shards[parts[p].shard];
-    for (uint32_t j = sh.job_begin; j < sh.job_end; j++, jo++) {
-      if (rc == BLSGPU_OK)
-        c->job_result[j] = res[jo];
-      else if (rc == BLSGPU_DEVICE_ERROR)  // a device failure rejects every job, never `false`
-        c->job_result[j] = -BLSGPU_DEVICE_ERROR;
-    }
-    blsgpu_stats& cs = c->sst[parts[p].shard];
+    blsgpu_stats& cs = parts[p].call->sst[parts[p].shard];
     if (k == 0) {
       cs = st;  // the merged run's counters (and stage times) go to its first call
     } else {
@@ -375,34 +181,57 @@ void run_merged(Device& d, Slot& sl, const std::vector<Task>& parts, std::vector
   }
 }
 
-void run_task(Device& d, Slot& sl, const Task& t) {
+// One shard as its own run; returns its status code.  The caller holds the device's table lock (shared).
+int run_task(Device& d, Slot& sl, const Task& t) {
   Call* c = t.call;
   const Shard& sh = c->shards[t.shard];
-  int rc;
-  if (c->ctx->closed && !c->sync) {
-    rc = BLSGPU_ERR_CLOSED;
-  } else {
-    try {
-      std::shared_lock<std::shared_mutex> tl(d.table_mu);
-      if (!table_covers(d, c, sh)) {
-        rc = BLSGPU_ERR_ARGS;
-      } else {
-        std::vector<uint64_t> scal(std::max<uint32_t>(sh.set_end - sh.set_begin, 1));
-        shard_scalars(c->b, sh, c->key, scal.data());
-        rc = run_call_shard(d, sl, c->b, sh, c->job_result, c->seed, c->opt, c->max_index, c->sst[t.shard],
-                            scal.data());
-        c->sst[t.shard].run_calls = 1;
-        c->sst[t.shard].urgent_lane = sl.urgent ? 1 : 0;
-      }
-    } catch (...) {
-      rc = BLSGPU_DEVICE_ERROR;
-    }
+  if (c->ctx->closed && !c->sync) return BLSGPU_ERR_CLOSED;
+  if (!table_covers(d, c, sh)) return BLSGPU_ERR_ARGS;
+  try {
+    std::vector<uint64_t> scal(std::max<uint32_t>(sh.set_end - sh.set_begin, 1));
+    shard_scalars(c->b, sh, c->key, scal.data());
+    const int rc = run_call_shard(d, sl, c->b, sh, c->job_result, c->seed, c->opt, c->max_index, c->sst[t.shard],
+                                  scal.data());
+    c->sst[t.shard].run_calls = 1;
+    return rc;
+  } catch (...) {
+    return BLSGPU_DEVICE_ERROR;
   }
-  if (rc == BLSGPU_DEVICE_ERROR)  // a device failure rejects every job of the shard, never `false`
-    for (uint32_t j = sh.job_begin; j < sh.job_end; j++) c->job_result[j] = -BLSGPU_DEVICE_ERROR;
-  c->rc[t.shard] = rc;
-  d.load.fetch_sub(sh.cost, std::memory_order_relaxed);
-  if (c->remaining.fetch_sub(1) == 1) finish_call(c);
+}
+
+// a device failure rejects every job of the shard, never `false`
+void reject_shard(const Task& t) {
+  const Shard& sh = t.call->shards[t.shard];
+  for (uint32_t j = sh.job_begin; j < sh.job_end; j++) t.call->job_result[j] = -BLSGPU_DEVICE_ERROR;
+}
+
+// Completes the parts of a run with their status codes: a device error rejects every job of the part; the call whose
+// last shard this was is finished.  lane: the urgent lane's run.
+void complete_parts(Device& d, const std::vector<Task>& parts, const std::vector<int>& rcs, bool lane) {
+  for (size_t p = 0; p < parts.size(); p++) {
+    Call* c = parts[p].call;
+    if (rcs[p] == BLSGPU_DEVICE_ERROR) reject_shard(parts[p]);
+    c->rc[parts[p].shard] = rcs[p];
+    c->sst[parts[p].shard].urgent_lane = lane ? 1 : 0;
+    d.load.fetch_sub(c->shards[parts[p].shard].cost, std::memory_order_relaxed);  // (an urgent lane's shard costs 0)
+    if (c->remaining.fetch_sub(1) == 1) finish_call(c);
+  }
+}
+
+// Runs the parts a dispatcher formed -- one as its own run, several as one merged run -- on its slot (sl.urgent: the
+// urgent lane's) and completes their calls.
+void run_parts(Device& d, Slot& sl, const std::vector<Task>& parts) {
+  std::vector<int> rcs(parts.size(), BLSGPU_OK);
+  try {
+    std::shared_lock<std::shared_mutex> tl(d.table_mu);
+    if (parts.size() == 1)
+      rcs[0] = run_task(d, sl, parts[0]);
+    else
+      run_merged(d, sl, parts, rcs);
+  } catch (...) {  // the runs catch their own failures; this only guards the lock
+    rcs.assign(parts.size(), BLSGPU_DEVICE_ERROR);
+  }
+  complete_parts(d, parts, rcs, sl.urgent);
 }
 
 inline uint32_t task_sets(const Task& t) {
@@ -412,7 +241,7 @@ inline uint32_t task_sets(const Task& t) {
 
 // A slot's dispatcher: takes the oldest queued shard of its device, merges the compatible shards queued behind it
 // (up to merge_sets sets), runs them, completes their calls.  Exits when the device stops (queue drained) or when
-// the slot is retired (option "slots" lowered).
+// the slot is retired (option `slots` lowered).
 void worker_loop(Device* d, Slot* sl) {
   tl_dispatcher = true;
   pthread_setname_np(pthread_self(), "blsgpu-slot");  // host-cost accounting by thread (bench.py "host")
@@ -489,27 +318,7 @@ void worker_loop(Device* d, Slot* sl) {
       Slot* sl;
       ~InflightGuard() { release_inflight(*d, *sl); }
     } guard{d, sl};
-    if (parts.size() == 1) {
-      run_task(*d, *sl, parts[0]);
-      continue;
-    }
-    std::vector<int> rcs(parts.size(), BLSGPU_OK);
-    try {
-      std::shared_lock<std::shared_mutex> tl(d->table_mu);
-      run_merged(*d, *sl, parts, rcs);
-    } catch (...) {  // run_merged catches its own failures; this only guards the lock
-      for (size_t p = 0; p < parts.size(); p++) {
-        const Shard& sh = parts[p].call->shards[parts[p].shard];
-        for (uint32_t j = sh.job_begin; j < sh.job_end; j++) parts[p].call->job_result[j] = -BLSGPU_DEVICE_ERROR;
-        rcs[p] = BLSGPU_DEVICE_ERROR;
-      }
-    }
-    for (size_t p = 0; p < parts.size(); p++) {
-      Call* c = parts[p].call;
-      c->rc[parts[p].shard] = rcs[p];
-      d->load.fetch_sub(c->shards[parts[p].shard].cost, std::memory_order_relaxed);
-      if (c->remaining.fetch_sub(1) == 1) finish_call(c);
-    }
+    run_parts(*d, *sl, parts);
   }
 }
 
@@ -563,41 +372,11 @@ void urgent_loop(Device* d, Slot* sl) {
     sl->alone = true;
     tl_run_t0 = std::chrono::steady_clock::now();
     tl_merge_ms = 0;
-    const size_t np = parts.size();
-    if (!ensure_urgent_streams(d, sl)) {  // no streams: every call of the run completes with a device error
-      for (size_t p = 0; p < np; p++) {
-        Call* c = parts[p].call;
-        const Shard& sh = c->shards[parts[p].shard];
-        for (uint32_t j = sh.job_begin; j < sh.job_end; j++) c->job_result[j] = -BLSGPU_DEVICE_ERROR;
-        c->rc[parts[p].shard] = BLSGPU_DEVICE_ERROR;
-        c->sst[parts[p].shard].urgent_lane = 1;
-        if (c->remaining.fetch_sub(1) == 1) finish_call(c);
-      }
-      d->upending.fetch_sub((int)np, std::memory_order_relaxed);
-      continue;
-    }
-    if (np == 1) {
-      run_task(*d, *sl, parts[0]);  // completes the call
-    } else {
-      std::vector<int> rcs(np, BLSGPU_OK);
-      try {
-        std::shared_lock<std::shared_mutex> tl(d->table_mu);
-        run_merged(*d, *sl, parts, rcs);
-      } catch (...) {  // run_merged catches its own failures; this only guards the lock
-        for (size_t p = 0; p < np; p++) {
-          const Shard& sh = parts[p].call->shards[parts[p].shard];
-          for (uint32_t j = sh.job_begin; j < sh.job_end; j++) parts[p].call->job_result[j] = -BLSGPU_DEVICE_ERROR;
-          rcs[p] = BLSGPU_DEVICE_ERROR;
-        }
-      }
-      for (size_t p = 0; p < np; p++) {
-        Call* c = parts[p].call;
-        c->rc[parts[p].shard] = rcs[p];
-        c->sst[parts[p].shard].urgent_lane = 1;
-        if (c->remaining.fetch_sub(1) == 1) finish_call(c);
-      }
-    }
-    d->upending.fetch_sub((int)np, std::memory_order_relaxed);
+    if (!ensure_urgent_streams(d, sl))  // no streams: every call of the run completes with a device error
+      complete_parts(*d, parts, std::vector<int>(parts.size(), BLSGPU_DEVICE_ERROR), true);
+    else
+      run_parts(*d, *sl, parts);
+    d->upending.fetch_sub((int)parts.size(), std::memory_order_relaxed);
   }
 }
 
@@ -628,10 +407,10 @@ hipStream_t make_stream(const std::vector<uint32_t>& mask, int prio) {
   return st;
 }
 
-// The device's pipeline streams and its urgent lane's (created with the first call, so "urgent_cus" set after init
+// The device's pipeline streams and its urgent lane's (created with the first call, so `urgent_cus` set after init
 // applies).  The urgent streams are CU-masked streams (hipExtStreamCreateWithCUMask), which HIP gives hardware queues
 // of their own: an urgent kernel never waits in a queue behind a pipeline kernel, only for free SIMDs.  Their mask is
-// every CU, or with "urgent_cus" > 0 a partition, mask bits [0, urgent_cus): the driver deals mask bits round-robin
+// every CU, or with `urgent_cus` > 0 a partition, mask bits [0, urgent_cus): the driver deals mask bits round-robin
 // over the XCDs (bit i -> XCD i % 8 in SPX mode, then over each XCD's shader engines; profiles/r06_cu_probe.json), so a
 // multiple of 8 bits gives every XCD the same number of partition CUs -- a workgroup is dealt to any XCD, and an XCD
 // without a CU of the stream's mask would never run it.  With urgent_isolate 1 the pipeline streams (and the slots'
@@ -745,7 +524,7 @@ void resize_slots(Device* d, int64_t want) {
     }
   }
   d->q_cv.notify_all();
-  // (set_option refuses "slots" on a dispatcher thread, so no thread joins itself here; a failing join leaves the
+  // (set_option refuses `slots` on a dispatcher thread, so no thread joins itself here; a failing join leaves the
   // retired dispatcher to finish on its own and keeps its slot: detached, never destroyed while joinable)
   for (size_t k = 0; k < joins.size(); k++) {
     try {
@@ -795,7 +574,7 @@ int64_t hw_queues_of_process() {
 // kernels.
 int64_t default_slots(int64_t) { return 3; }
 
-// Creates the devices' slots on the first call (so a "slots" value set after init is the count created).
+// Creates the devices' slots on the first call (so a `slots` value set after init is the count created).
 int ensure_slots(blsgpu_ctx* ctx) {
   std::lock_guard<std::mutex> lk(ctx->slots_mu);
   if (ctx->slots_started) return BLSGPU_OK;
@@ -833,13 +612,6 @@ int ensure_slots(blsgpu_ctx* ctx) {
   return BLSGPU_OK;
 }
 
-// Routes a call (whole, or split over the least-loaded devices: route_rule) and queues the shard tasks.
-int64_t shard_cost(const blsgpu_batch& b, const Shard& sh) {
-  int64_t c = 256 * (int64_t)(sh.set_end - sh.set_begin);
-  if (b.set_pk_first) c += b.set_pk_first[sh.set_end] - b.set_pk_first[sh.set_begin];
-  return c;
-}
-
 // An urgent call (a BLSGPU_JOB_URGENT job) of <= urgent_max_sets sets goes whole to the urgent lane of the device with
 // the fewest urgent calls pending (ties rotate); a larger one is routed as any call but queued at the head of each
 // device's queue.  Returns true when the call was queued on an urgent lane.
@@ -873,6 +645,7 @@ bool launch_urgent(blsgpu_ctx* ctx, Call* c) {
   return true;
 }
 
+// Routes a call (whole, or split over the least-loaded devices: call_plan.hpp route_rule) and queues the shard tasks.
 void launch_call(blsgpu_ctx* ctx, Call* c) {
   const blsgpu_batch& b = c->b;
   bool urgent = false;
@@ -1076,26 +849,12 @@ int blsgpu_pubkeys_upload(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* 
   return result;
 }
 
+// The options of the table (options.hpp kOptionRows) are stored in ctx->opt under opt_mu; the keys that live on the
+// context itself (CtxKey) are handled here by name.
 int blsgpu_set_option(blsgpu_ctx* ctx, const char* key, int64_t value) {
   if (!ctx || !key) return BLSGPU_ERR_ARGS;
-  std::string k(key);
-  if (k == "urgent_cus" || k == "urgent_isolate" || k == "blocking_sync" || k == "pipeline_prio") {
-    // stream / event creation: before the first call only
-    std::lock_guard<std::mutex> sk(ctx->slots_mu);
-    if (ctx->slots_started) return BLSGPU_ERR_ARGS;
-    if (k == "blocking_sync" || k == "pipeline_prio") {
-      if (value < 0 || value > 1) return BLSGPU_ERR_ARGS;
-      (k == "blocking_sync" ? ctx->blocking_sync : ctx->pipeline_prio) = value;
-    } else if (k == "urgent_cus") {
-      if (value < 0 || value > 128 || (value & 7)) return BLSGPU_ERR_ARGS;
-      ctx->urgent_cus = value;
-    } else {
-      if (value < 0 || value > 3) return BLSGPU_ERR_ARGS;
-      ctx->urgent_isolate = value;
-    }
-    return BLSGPU_OK;
-  }
-  if (k == "slots") {
+  const CtxKey k = ctx_key(key);
+  if (k == CtxKey::slots) {
     // not from a dispatcher thread (a done callback): retiring its own slot would join itself
     if (value < 1 || value > 64 || tl_dispatcher) return BLSGPU_ERR_ARGS;
     std::lock_guard<std::mutex> sk(ctx->slots_mu);
@@ -1109,213 +868,72 @@ int blsgpu_set_option(blsgpu_ctx* ctx, const char* key, int64_t value) {
     }
     return BLSGPU_OK;
   }
-  std::lock_guard<std::mutex> lk(ctx->opt_mu);
-  if (k == "group_sets") {
-    if (value < 1) return BLSGPU_ERR_ARGS;
-    ctx->opt.group_sets = value;
-  } else if (k == "profile") {
-    ctx->opt.profile = value != 0;
-  } else if (k == "max_devices") {
-    if (value < 1) return BLSGPU_ERR_ARGS;
-    ctx->opt.max_devices = value;
-  } else if (k == "dedupe") {
-    ctx->opt.dedupe = value != 0;
-  } else if (k == "merge_sets") {
-    if (value < 0) return BLSGPU_ERR_ARGS;
-    ctx->opt.merge_sets = value;
-  } else if (k == "miller_k") {
-    if (value < 0 || value > 64) return BLSGPU_ERR_ARGS;
-    ctx->opt.miller_k = value;
-  } else if (k == "group_policy") {
-    if (value < 0 || value > 1) return BLSGPU_ERR_ARGS;
-    ctx->opt.group_policy = value;
-  } else if (k == "merge_wait_us") {
-    if (value < 0 || value > 1000000) return BLSGPU_ERR_ARGS;
-    ctx->opt.merge_wait_us = value;
-  } else if (k == "idle_wait_us") {
-    if (value < 0 || value > 1000000) return BLSGPU_ERR_ARGS;
-    ctx->opt.idle_wait_us = value;
-  } else if (k == "pipeline_depth") {
-    if (value < 1 || value > 64) return BLSGPU_ERR_ARGS;
-    ctx->opt.pipeline_depth = value;
-  } else if (k == "serial") {
-    ctx->opt.serial = value != 0;
-  } else if (k == "miller_lanes") {
-    if (value < 0 || (value > 3 && value != 6)) return BLSGPU_ERR_ARGS;
-    ctx->opt.miller_lanes = value;
-  } else if (k == "msm_slice_mid") {
-    if (value < 8 || value > MSM_SLICE) return BLSGPU_ERR_ARGS;
-    ctx->opt.msm_slice_mid = value;
-  } else if (k == "copy_stream") {
-    ctx->opt.copy_stream = value != 0;
-  } else if (k == "tail_on_msg") {
-    ctx->opt.tail_on_msg = value != 0;
-  } else if (k == "early_release") {
-    ctx->opt.early_release = value != 0;
-  } else if (k == "merge_balance") {
-    ctx->opt.merge_balance = value != 0;
-  } else if (k == "lines_lanes") {
-    if (value < 1 || value > 2) return BLSGPU_ERR_ARGS;
-    ctx->opt.lines_lanes = value;
-  } else if (k == "msm_tree") {
-    ctx->opt.msm_tree = value != 0;
-  } else if (k == "coop_max") {
-    if (value < 0 || value > (1 << 24)) return BLSGPU_ERR_ARGS;
-    ctx->opt.coop_max = value;
-  } else if (k == "coop_g2_max") {
-    if (value < 0 || value > (1 << 24)) return BLSGPU_ERR_ARGS;
-    ctx->opt.coop_g2_max = value;
-  } else if (k == "coop_excl_max") {
-    if (value < 0 || value > (1 << 24)) return BLSGPU_ERR_ARGS;
-    ctx->opt.coop_excl_max = value;
-  } else if (k == "rsig_spec") {
-    ctx->opt.rsig_spec = value != 0;
-  } else if (k == "spec_large") {
-    ctx->opt.spec_large = value != 0;
-  } else if (k == "spec_gsm") {
-    ctx->opt.spec_gsm = value != 0;
-  } else if (k == "fb_lane_min") {
-    if (value < 0) return BLSGPU_ERR_ARGS;
-    ctx->opt.fb_lane_min = value;
-  } else if (k == "fb_force_busy") {
-    ctx->opt.fb_force_busy = value != 0;
-  } else if (k == "keep_f") {
-    ctx->opt.keep_f = value != 0;
-  } else if (k == "keep_copy") {
-    ctx->opt.keep_copy = value != 0;
-  } else if (k == "urgent_lane") {
-    ctx->opt.urgent_lane = value != 0;
-  } else if (k == "urgent_max_sets") {
-    if (value < 0) return BLSGPU_ERR_ARGS;
-    ctx->opt.urgent_max_sets = value;
-  } else if (k == "urgent_excl") {
-    ctx->opt.urgent_excl = value != 0;
-  } else if (k == "group_adapt") {
-    ctx->opt.group_adapt = value != 0;
-  } else if (k == "urgent_wait_us") {
-    if (value < 0 || value > 100000) return BLSGPU_ERR_ARGS;
-    ctx->opt.urgent_wait_us = value;
-  } else if (k == "fb_check6") {
-    if (value < 0 || value > 2) return BLSGPU_ERR_ARGS;
-    ctx->opt.fb_check6 = value;
-  } else if (k == "fb_direct_min") {
-    if (value < 0) return BLSGPU_ERR_ARGS;
-    ctx->opt.fb_direct_min = value;
-  } else if (k == "small_max") {
-    if (value < 0) return BLSGPU_ERR_ARGS;
-    ctx->opt.small_max = value;
-  } else if (k == "miller_pairs") {
-    if (value < 0 || value > 1) return BLSGPU_ERR_ARGS;
-    ctx->opt.miller_pairs = value;
-  } else if (k == "acc6_max") {
-    if (value < 0) return BLSGPU_ERR_ARGS;
-    ctx->opt.acc6_max = value;
-  } else if (k == "route_split_sets") {
-    if (value < 1) return BLSGPU_ERR_ARGS;
-    ctx->opt.route_split_sets = value;
-  } else if (k == "lane_tail_parts") {
-    if (value < 0 || value > 3) return BLSGPU_ERR_ARGS;
-    ctx->opt.lane_tail_parts = value;
-  } else if (k == "lane_tail_min") {
-    if (value < 0) return BLSGPU_ERR_ARGS;
-    ctx->opt.lane_tail_min = value;
-  } else if (k == "f_run_max") {
-    if (value < 1 || value > 1024 || (value & (value - 1))) return BLSGPU_ERR_ARGS;
-    ctx->opt.f_run_max = value;
-  } else {
-    return BLSGPU_ERR_ARGS;
+  if (k != CtxKey::none) {
+    // stream / event creation: before the first call only
+    std::lock_guard<std::mutex> sk(ctx->slots_mu);
+    if (ctx->slots_started) return BLSGPU_ERR_ARGS;
+    switch (k) {
+      case CtxKey::blocking_sync:
+      case CtxKey::pipeline_prio:
+        if (value < 0 || value > 1) return BLSGPU_ERR_ARGS;
+        (k == CtxKey::blocking_sync ? ctx->blocking_sync : ctx->pipeline_prio) = value;
+        return BLSGPU_OK;
+      case CtxKey::urgent_cus:
+        if (value < 0 || value > 128 || (value & 7)) return BLSGPU_ERR_ARGS;
+        ctx->urgent_cus = value;
+        return BLSGPU_OK;
+      case CtxKey::urgent_isolate:
+        if (value < 0 || value > 3) return BLSGPU_ERR_ARGS;
+        ctx->urgent_isolate = value;
+        return BLSGPU_OK;
+      default:  // the read-only keys
+        return BLSGPU_ERR_ARGS;
+    }
   }
-  return BLSGPU_OK;
+  const OptionRow* row = find_option(key, true);
+  if (!row) return BLSGPU_ERR_ARGS;
+  std::lock_guard<std::mutex> lk(ctx->opt_mu);
+  return store_option(ctx->opt, *row, value) ? BLSGPU_OK : BLSGPU_ERR_ARGS;
 }
 
 int blsgpu_get_option(const blsgpu_ctx* cctx, const char* key, int64_t* value) {
   if (!cctx || !key || !value) return BLSGPU_ERR_ARGS;
   blsgpu_ctx* ctx = const_cast<blsgpu_ctx*>(cctx);
-  const std::string k(key);
-  if (k == "slots") {
-    std::lock_guard<std::mutex> sk(ctx->slots_mu);
-    if (ctx->slots_started && !ctx->devs.empty()) {
-      std::lock_guard<std::mutex> lk(ctx->devs[0]->q_mu);
-      *value = (int64_t)ctx->devs[0]->slots.size();
-    } else {
-      *value = ctx->slots_per_device;
-    }
+  const CtxKey k = ctx_key(key);
+  if (k == CtxKey::none) {
+    const OptionRow* row = find_option(key, true);
+    if (!row) return BLSGPU_ERR_ARGS;
+    std::lock_guard<std::mutex> lk(ctx->opt_mu);
+    *value = ctx->opt.*row->member;
     return BLSGPU_OK;
   }
-  if (k == "hw_queues") {
+  if (k == CtxKey::hw_queues) {
     *value = ctx->hw_queues;
-    return BLSGPU_OK;
-  }
-  if (k == "blocking_sync" || k == "pipeline_prio") {
-    std::lock_guard<std::mutex> sk(ctx->slots_mu);
-    *value = k == "blocking_sync" ? ctx->blocking_sync : ctx->pipeline_prio;
-    return BLSGPU_OK;
-  }
-  if (k == "urgent_cus" || k == "urgent_isolate") {
-    std::lock_guard<std::mutex> sk(ctx->slots_mu);
-    // once the streams exist: the partition device 0 was created with (0 when the device is too small for it)
-    if (k == "urgent_cus")
-      *value = ctx->slots_started && !ctx->devs.empty() ? ctx->devs[0]->urgent_cus : ctx->urgent_cus;
-    else
-      *value = ctx->urgent_isolate;
-    return BLSGPU_OK;
-  }
-  if (k == "abi_version") {
+  } else if (k == CtxKey::abi_version) {
     *value = BLSGPU_ABI_VERSION;
-    return BLSGPU_OK;
-  }
-  if (k == "spurious_groups") {
+  } else if (k == CtxKey::spurious_groups) {
     uint64_t c = 0;
     for (const Device* d : ctx->devs) c += d->spurious_groups.load(std::memory_order_relaxed);
     *value = (int64_t)c;
-    return BLSGPU_OK;
+  } else {
+    std::lock_guard<std::mutex> sk(ctx->slots_mu);
+    const bool started = ctx->slots_started && !ctx->devs.empty();
+    if (k == CtxKey::slots) {
+      if (started) {
+        std::lock_guard<std::mutex> lk(ctx->devs[0]->q_mu);
+        *value = (int64_t)ctx->devs[0]->slots.size();
+      } else {
+        *value = ctx->slots_per_device;
+      }
+    } else if (k == CtxKey::urgent_cus) {
+      // once the streams exist: the partition device 0 was created with (0 when the device is too small for it)
+      *value = started ? ctx->devs[0]->urgent_cus : ctx->urgent_cus;
+    } else {
+      *value = k == CtxKey::urgent_isolate ? ctx->urgent_isolate
+               : k == CtxKey::blocking_sync ? ctx->blocking_sync
+                                            : ctx->pipeline_prio;
+    }
   }
-  std::lock_guard<std::mutex> lk(ctx->opt_mu);
-  const Options& o = ctx->opt;
-  if (k == "group_sets") *value = o.group_sets;
-  else if (k == "profile") *value = o.profile;
-  else if (k == "max_devices") *value = o.max_devices;
-  else if (k == "dedupe") *value = o.dedupe;
-  else if (k == "merge_sets") *value = o.merge_sets;
-  else if (k == "miller_k") *value = o.miller_k;
-  else if (k == "group_policy") *value = o.group_policy;
-  else if (k == "merge_wait_us") *value = o.merge_wait_us;
-  else if (k == "idle_wait_us") *value = o.idle_wait_us;
-  else if (k == "pipeline_depth") *value = o.pipeline_depth;
-  else if (k == "serial") *value = o.serial;
-  else if (k == "miller_lanes") *value = o.miller_lanes;
-  else if (k == "f_run_max") *value = o.f_run_max;
-  else if (k == "lane_tail_min") *value = o.lane_tail_min;
-  else if (k == "lane_tail_parts") *value = o.lane_tail_parts;
-  else if (k == "msm_slice_mid") *value = o.msm_slice_mid;
-  else if (k == "msm_tree") *value = o.msm_tree;
-  else if (k == "lines_lanes") *value = o.lines_lanes;
-  else if (k == "merge_balance") *value = o.merge_balance;
-  else if (k == "early_release") *value = o.early_release;
-  else if (k == "tail_on_msg") *value = o.tail_on_msg;
-  else if (k == "copy_stream") *value = o.copy_stream;
-  else if (k == "coop_max") *value = o.coop_max;
-  else if (k == "coop_g2_max") *value = o.coop_g2_max;
-  else if (k == "coop_excl_max") *value = o.coop_excl_max;
-  else if (k == "rsig_spec") *value = o.rsig_spec;
-  else if (k == "spec_large") *value = o.spec_large;
-  else if (k == "spec_gsm") *value = o.spec_gsm;
-  else if (k == "fb_lane_min") *value = o.fb_lane_min;
-  else if (k == "route_split_sets") *value = o.route_split_sets;
-  else if (k == "acc6_max") *value = o.acc6_max;
-  else if (k == "miller_pairs") *value = o.miller_pairs;
-  else if (k == "small_max") *value = o.small_max;
-  else if (k == "fb_direct_min") *value = o.fb_direct_min;
-  else if (k == "fb_check6") *value = o.fb_check6;
-  else if (k == "fb_force_busy") *value = o.fb_force_busy;
-  else if (k == "keep_f") *value = o.keep_f;
-  else if (k == "keep_copy") *value = o.keep_copy;
-  else if (k == "urgent_lane") *value = o.urgent_lane;
-  else if (k == "urgent_max_sets") *value = o.urgent_max_sets;
-  else if (k == "urgent_excl") *value = o.urgent_excl;
-  else if (k == "urgent_wait_us") *value = o.urgent_wait_us;
-  else if (k == "group_adapt") *value = o.group_adapt;
-  else return BLSGPU_ERR_ARGS;
   return BLSGPU_OK;
 }
 

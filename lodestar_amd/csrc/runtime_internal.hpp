@@ -1,4 +1,5 @@
-// Host types the translation units of the runtime share: runtime.cpp (calls, sharding, dispatchers, options, the ABI),
+// Host types the translation units of the runtime share: runtime.cpp (contexts, devices, slots, dispatchers, uploads,
+// the ABI; the call side's arithmetic is call_plan.hpp, the options table options.hpp),
 // pipeline.cpp (one pipeline run: run_call_shard) and helpers.cpp (the synchronous helper calls).  Nothing here is
 // part of the C ABI (include/blsgpu.h): the namespace is hidden, so none of it reaches the library's dynamic symbol
 // table.
@@ -21,7 +22,8 @@
 #include "../../include/blsgpu.h"
 #include "batch_rand.hpp"
 #include "kernels.h"
-#include "run_plan.hpp"  // Options, Shard, MsgIndex, al256 and the plan of a pipeline run: the HIP-free side
+#include "run_plan.hpp"  // Options (options.hpp), Shard, pk_mode, MsgIndex, al256 and the plan of a pipeline run: the
+                         // HIP-free side
 
 namespace blsgpu_rt __attribute__((visibility("hidden"))) {
 
@@ -270,7 +272,7 @@ struct Device {
   // Urgent lane (BLSGPU_JOB_URGENT, the reference's verifyOnMainThread): one slot with its own dispatcher and two stream
   // pairs, taking urgent calls from uqueue (under q_mu) one at a time.  It never counts in runs_inflight and never takes
   // enq_mu, so an urgent call waits for no throughput run on the host; on the device its streams either run on a
-  // reserved CU partition that the pipeline streams are masked off ("urgent_cus" > 0) or at the highest priority.
+  // reserved CU partition that the pipeline streams are masked off (`urgent_cus` > 0) or at the highest priority.
   hipStream_t ust[4] = {};         // the urgent lane's streams, created by its dispatcher before its first run
   std::vector<uint32_t> umask;      // their CU mask (empty: plain streams of priority uprio)
   int uprio = 0;
@@ -279,7 +281,7 @@ struct Device {
   std::thread uworker;
   std::atomic<int> upending{0};  // urgent calls queued or running here (routing of urgent calls)
   // batch groups whose equation failed although every job of theirs verified on its own in the fallback -- zero unless a
-  // kernel computed a group's equation wrong (read-only option "spurious_groups"; each one is also logged)
+  // kernel computed a group's equation wrong (read-only option `spurious_groups`; each one is also logged)
   std::atomic<uint64_t> spurious_groups{0};
   int urgent_cus = 0;            // CUs of the partition the streams were created with (0 = none)
   std::vector<uint32_t> main_mask;  // CU mask of the pipeline and fallback streams (empty = all CUs, priorities)
@@ -295,9 +297,6 @@ inline double ms_since(std::chrono::steady_clock::time_point t) {
 // The call's scalar key and message-index hash key from its seed (batch_rand.hpp): seed 0 = 256 bits of OS
 // entropy, else the comparison-run key of the seed.  false = no entropy: the call must fail (never a constant).
 bool resolve_key(uint64_t seed, batch_rand::Key& key, uint64_t& hash_key);  // runtime.cpp
-
-// pubkey mode of a batch: 0 table, 1 one key per set (bytes), 2 bytes aggregate
-inline int pk_mode(const blsgpu_batch& b) { return !b.pk_bytes ? 0 : (b.set_pk_first ? 2 : 1); }
 
 // pipeline.cpp: one shard of a call (or a merged batch) as one pipeline run on a slot, under the call's group policy
 // (writes job_result[job_begin .. job_end)); and the run's leaving the device's in-flight count (once)

@@ -3,7 +3,7 @@
 The path shards by independent units: each job yields its own boolean, so jobs are split
 into contiguous ranges balanced by estimated cost (1 per set + 1/256 per aggregated pubkey), never
 splitting a job, with no collective on the data path.  This is the same rule the C++ runtime applies to
-the devices of one process (lodestar_amd/csrc/runtime.cpp, `cost-balanced contiguous sharding`); the
+the devices of one process (lodestar_amd/csrc/call_plan.hpp shard_rule, `cost-balanced contiguous sharding`); the
 multi-process bench (bench.py --config C4) and the world_size-2 gloo test use this restatement.
 """
 import numpy as np
@@ -38,7 +38,7 @@ def shard_jobs(job_first_set, n_shards, set_pk_first=None):
 
 
 def route_call(n_sets, device_load, split_sets=16384, start=0):
-    """Which devices a call runs on (the runtime's route_rule, runtime.cpp; C-ABI blsgpu_route_call): k =
+    """Which devices a call runs on (the runtime's route_rule, csrc/call_plan.hpp; C-ABI blsgpu_route_call): k =
     min(devices, max(1, n_sets // split_sets)) -- a call below 2 x split_sets sets runs WHOLE on one device -- chosen
     as the k least loaded, ties broken by distance from `start`, returned in ascending order (shard order)."""
     n = len(device_load)

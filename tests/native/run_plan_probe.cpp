@@ -23,27 +23,48 @@ void put_ftree(Handle& h, const FTree& t) {
   h.num["n_fruns"] = t.n_fruns, h.num["f_k"] = t.f_k, h.num["n_franges"] = t.n_franges;
 }
 
-bool set_option(Options& o, const std::string& k, int64_t v) {
-#define OPT(name)     \
-  if (k == #name) {   \
-    o.name = v;       \
-    return true;      \
-  }
-  OPT(group_sets) OPT(dedupe) OPT(miller_k) OPT(serial) OPT(miller_segments) OPT(miller_lanes) OPT(f_run_max)
-  OPT(lane_tail_min) OPT(msm_slice_mid) OPT(msm_tree) OPT(coop_max) OPT(coop_g2_max) OPT(coop_excl_max) OPT(rsig_spec)
-  OPT(spec_large) OPT(fb_lane_min) OPT(acc6_max) OPT(miller_pairs) OPT(small_max) OPT(fb_direct_min) OPT(keep_f)
-  OPT(fb_force_busy) OPT(urgent_excl) OPT(group_adapt)
-#undef OPT
-  return false;
-}
+constexpr int kRows = sizeof kOptionRows / sizeof kOptionRows[0];
 
 }  // namespace
 
 extern "C" {
 
 void* rp_options_new() { return new Options(); }
-int rp_option(void* o, const char* key, int64_t v) { return set_option(*static_cast<Options*>(o), key, v) ? 0 : -1; }
+// any row of the options table by name (options.hpp), the raw value with no range check
+int rp_option(void* o, const char* key, int64_t v) {
+  const OptionRow* r = find_option(key, false);
+  if (r) static_cast<Options*>(o)->*r->member = v;
+  return r ? 0 : -1;
+}
+// as blsgpu_set_option stores it: -1 = refused (no such ABI key, or the value is out of range), nothing changed
+int rp_option_checked(void* o, const char* key, int64_t v) {
+  const OptionRow* r = find_option(key, true);
+  return r && store_option(*static_cast<Options*>(o), *r, v) ? 0 : -1;
+}
+int rp_option_get(const void* o, const char* key, int64_t* v) {
+  const OptionRow* r = find_option(key, false);
+  if (r) *v = static_cast<const Options*>(o)->*r->member;
+  return r ? 0 : -1;
+}
+int rp_options_same_run(const void* a, const void* b) {
+  return static_cast<const Options*>(a)->same_run(*static_cast<const Options*>(b));
+}
 void rp_options_free(void* o) { delete static_cast<Options*>(o); }
+// the table's rows, i = 0, 1, ...: the key (null past the last row), whether it is an ABI key, whether it takes part
+// in same_run, its default
+const char* rp_option_key(int i) { return i >= 0 && i < kRows ? kOptionRows[i].key : nullptr; }
+int rp_option_abi(int i) { return kOptionRows[i].abi; }
+int rp_option_same_run(int i) { return kOptionRows[i].run; }
+int64_t rp_option_default(int i) { return Options().*kOptionRows[i].member; }
+// the keys outside the table, space-separated: those that live on the context (read_only 0), the read-only ones (1)
+const char* rp_extra_keys(int read_only) {
+  static std::string out[2];
+  std::string& s = out[read_only != 0];
+  s.clear();
+  for (int i = read_only ? kCtxKeysSettable : 0; i < (read_only ? (int)CtxKey::none : kCtxKeysSettable); i++)
+    s += std::string(s.empty() ? "" : " ") + kCtxKeys[i];
+  return s.c_str();
+}
 
 uint32_t rp_vec(void* h, const char* name, uint32_t* out, uint32_t cap) {
   const auto& m = static_cast<Handle*>(h)->vec;

@@ -11,7 +11,7 @@ SRC = os.path.join(HERE, "native", "run_plan_probe.cpp")
 LIB = os.path.join(HERE, "native", "librun_plan_probe.so")
 CSRC = os.path.join(os.path.dirname(HERE), "lodestar_amd", "csrc")
 HDR = os.path.join(CSRC, "run_plan.hpp")
-DEPS = [SRC, HDR, os.path.join(CSRC, "helper_layout.hpp"), os.path.join(CSRC, "miller_plan.hpp")]
+DEPS = [SRC, HDR] + [os.path.join(CSRC, h) for h in ("options.hpp", "helper_layout.hpp", "miller_plan.hpp")]
 
 _lib = None
 
@@ -25,6 +25,8 @@ def lib():
         for f in ("rp_options_new", "rp_plan", "rp_ftree", "rp_classify", "rp_fallback", "rp_pool"):
             getattr(L, f).restype = ctypes.c_void_p
         L.rp_next_fail_rate.restype = ctypes.c_double
+        L.rp_option_key.restype = L.rp_extra_keys.restype = ctypes.c_char_p
+        L.rp_option_default.restype = ctypes.c_int64
         _lib = L
     return _lib
 
@@ -73,8 +75,35 @@ class Opts:
         for k, v in kv.items():
             assert lib().rp_option(self.h, k.encode(), ctypes.c_int64(int(v))) == 0, k
 
+    def set_checked(self, key, value):
+        """As blsgpu_set_option stores it; False = refused."""
+        return lib().rp_option_checked(self.h, key.encode(), ctypes.c_int64(int(value))) == 0
+
+    def __getitem__(self, key):
+        v = ctypes.c_int64()
+        assert lib().rp_option_get(self.h, key.encode(), ctypes.byref(v)) == 0, key
+        return v.value
+
+    def same_run(self, other):
+        return bool(lib().rp_options_same_run(self.h, other.h))
+
     def __del__(self):
         lib().rp_options_free(self.h)
+
+
+def option_rows():
+    """The options table (csrc/options.hpp): [(key, is an ABI key, takes part in same_run, default)]."""
+    rows, i = [], 0
+    while lib().rp_option_key(i) is not None:
+        rows.append((lib().rp_option_key(i).decode(), bool(lib().rp_option_abi(i)), bool(lib().rp_option_same_run(i)),
+                     lib().rp_option_default(i)))
+        i += 1
+    return rows
+
+
+def extra_keys():
+    """(the keys that live on the context, the read-only keys): handled by name in runtime.cpp."""
+    return tuple(set(lib().rp_extra_keys(ro).decode().split()) for ro in (0, 1))
 
 
 def plan(counts, flags, msg_ids, *, opts=None, keys_per_set=None, pk_mode=1, sig_len=None, job_begin=0, job_end=None,

@@ -109,8 +109,8 @@ def test_entropy_failure_fails_closed():
 
 def test_no_constant_scalar_fallback_in_runtime():
     """The runtime has no public-constant or counter fallback for production scalars (the round-3 SEED fallback)."""
-    src = open(os.path.join(ROOT, "lodestar_amd", "csrc", "runtime.cpp")).read()
-    src += open(os.path.join(ROOT, "lodestar_amd", "csrc", "batch_rand.hpp")).read()
+    src = "".join(open(os.path.join(ROOT, "lodestar_amd", "csrc", f)).read()
+                  for f in ("runtime.cpp", "call_plan.hpp", "batch_rand.hpp"))
     assert "4c4f444553544152" not in src.lower()
     assert "splitmix" not in src.lower()
 

@@ -164,7 +164,7 @@ def test_mainnet_g2_corpus_in_pipeline(ctx, pool):
 
 
 def test_routing_whole_calls_and_split_epoch_calls(pool):
-    """Calls are routed, not sharded (runtime route_rule): on two device contexts a 16k gossip call runs whole on one
+    """Calls are routed, not sharded (call_plan.hpp route_rule): on two device contexts a 16k gossip call runs whole on one
     device, a 32,768-set call (C4's step) splits over both, and concurrent whole calls spread over the devices."""
     from concurrent.futures import ThreadPoolExecutor
 

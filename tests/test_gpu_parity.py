@@ -459,6 +459,61 @@ def test_merged_run_isolates_bad_call():
         c.close()
 
 
+@pytest.mark.parametrize("mode", [0, 2])
+def test_merged_run_of_unlike_calls_vs_oracle(mode):
+    """Six small calls (5, 1, 7, 5, 1 and 7 sets) that one slot merges into a pipeline run (call_plan.hpp
+    MergedBatch): they differ in signature stride (96, 192, 200) and form (the wider strides carry uncompressed
+    signatures), one set of one call signs another message, and every call's results are the oracle's for that call
+    alone.  mode: 0 table indices, 2 key bytes per set range."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from lodestar_amd.native import Context
+
+    sizes, jobs = [5, 1, 7, 5, 1, 7], {5: [0, 2, 5], 1: [0, 1], 7: [0, 3, 7]}
+    n = sum(sizes)
+    sks = interop_sks(n, first=300)
+    msgs = [msg(j, b"unlike") for j in range(n)]
+    sigs = cpu.sign(sks, b"".join(msgs), threads=THREADS)
+    pks = cpu.sk_to_pk(sks, threads=THREADS)
+    msgs[5 + 1 + 4] = msg(0, b"unlike other")  # the third call's second job signs something else
+    calls, at = [], 0
+    for q, ns in enumerate(sizes):
+        stride = (96, 192, 200)[q % 3]
+        rows, sig_len = [], []
+        for i in range(at, at + ns):
+            s = sigs[96 * i: 96 * i + 96]
+            if stride >= 192 and (i + q) % 2 == 0:  # the uncompressed form
+                s = bls.g2_serialize(bls.g2_decompress_raw(s)[0])
+            rows.append(s.ljust(stride, b"\xEE"))
+            sig_len.append(len(s))
+        call = dict(job_first_set=jobs[ns], sigs=b"".join(rows), sig_len=sig_len, msgs=b"".join(msgs[at:at + ns]),
+                    set_pk_first=np.arange(ns + 1), job_flags=np.ones(len(jobs[ns]) - 1), sig_stride=stride)
+        if mode == 0:
+            call["pk_index"] = np.arange(at, at + ns)
+        else:
+            call["pk_bytes"] = pks[96 * at: 96 * (at + ns)]
+        calls.append(call)
+        at += ns
+    assert any(192 in c["sig_len"] for c in calls) and any(96 in c["sig_len"] and c["sig_stride"] > 96 for c in calls)
+    table = cpu.Table(pks) if mode == 0 else None
+    want = [cpu.verify_jobs(table=table, threads=THREADS, **c)[0] for c in calls]
+    assert [w.tolist() for w in want] == [[1, 1], [1], [1, 0], [1, 1], [1], [1, 1]]
+    c = Context([0])
+    try:
+        c.set_option("slots", 1)
+        c.set_option("merge_sets", 1 << 20)
+        c.set_option("idle_wait_us", 200000)
+        if mode == 0:
+            c.upload_pubkeys(0, pks)
+        with ThreadPoolExecutor(len(calls)) as pool:
+            outs = [f.result() for f in [pool.submit(c.verify_raw, **call) for call in calls]]
+    finally:
+        c.close()
+    for q, (got, st) in enumerate(outs):
+        assert np.array_equal(got, want[q]), (q, got, want[q])
+    assert max(st.run_calls for _, st in outs) >= 2  # some calls shared a run
+
+
 @pytest.mark.parametrize("k,lanes", [(2, 2), (4, 2), (2, 1), (1, 1), (1, 6), (2, 6), (3, 6), (1, 3), (2, 3), (3, 3)])
 def test_miller_chunk_forms_vs_oracle(ctx, k, lanes):
     """The Miller accumulation's chunk forms: chunks of k pairings on six lanes (one w-basis coefficient of f each),

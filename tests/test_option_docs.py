@@ -1,18 +1,19 @@
-"""Every runtime option blsgpu_set_option accepts (lodestar_amd/csrc/runtime.cpp) is documented in include/blsgpu.h
-and listed in INTEGRATION.md, and the read-only keys blsgpu_get_option adds are the documented ones (host files
-only; tests/test_gpu_options.py exercises the keys on a device)."""
+"""Every runtime option blsgpu_set_option accepts (the options table and the context keys, lodestar_amd/csrc/
+options.hpp, read through tests/native/run_plan_probe.cpp) is documented in include/blsgpu.h and listed in
+INTEGRATION.md, and the read-only keys blsgpu_get_option adds are the documented ones (host files only;
+tests/test_gpu_options.py exercises the keys on a device)."""
 import os
 import re
+
+from tests import run_plan_probe as rp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _keys():
-    src = open(os.path.join(ROOT, "lodestar_amd", "csrc", "runtime.cpp")).read()
-    i, j = src.index("int blsgpu_set_option"), src.index("int blsgpu_get_option")
-    set_keys = set(re.findall(r'k == "([a-z0-9_]+)"', src[i:j]))
-    get_keys = set(re.findall(r'k == "([a-z0-9_]+)"', src[j:j + 10000]))
-    return set_keys, get_keys
+    context_keys, read_only = rp.extra_keys()
+    set_keys = {key for key, abi, _, _ in rp.option_rows() if abi} | context_keys
+    return set_keys, set_keys | read_only
 
 
 def test_every_option_documented():

@@ -43,10 +43,10 @@ def test_header_is_hip_free():
     includes = [ln.split()[1] for ln in src.splitlines() if ln.startswith("#include")]
     assert sorted(includes) == sorted(["<stddef.h>", "<stdint.h>", "<string.h>", "<algorithm>", "<cmath>", "<utility>",
                                        "<vector>", '"../../include/blsgpu.h"', '"helper_layout.hpp"',
-                                       '"miller_plan.hpp"'])
-    # and the three project headers it includes bring in none
+                                       '"miller_plan.hpp"', '"options.hpp"'])
+    # and the four project headers it includes bring in none
     for dep in (os.path.join(rp.CSRC, "helper_layout.hpp"), os.path.join(rp.CSRC, "miller_plan.hpp"),
-                os.path.join(os.path.dirname(rp.HERE), "include", "blsgpu.h")):
+                os.path.join(rp.CSRC, "options.hpp"), os.path.join(os.path.dirname(rp.HERE), "include", "blsgpu.h")):
         assert all("hip" not in ln and '"' not in ln for ln in open(dep).read().splitlines() if ln.startswith("#include"))
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Isolated-call latency and loaded throughput of gossip-shaped calls (C2 shape: one single-pubkey batchable set per
 job, distinct messages) across call sizes and runtime-option variants -- the data for the cooperative-form thresholds
-(runtime.cpp coop_max / coop_g2_max / coop_excl_max).
+(options.hpp coop_max / coop_g2_max / coop_excl_max).
 
     python tools/latency_curve.py --sizes 512,1024,2048 --variants 'base:;coop2k:coop_max=2048,coop_g2_max=2048' \
         [--invalid 0.01] [--inflight 32 --load-steps 200] --out gpurun_out/curve.json
