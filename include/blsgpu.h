@@ -27,7 +27,11 @@
  *                                      validateGossipAttestationsSameAttData)
  *   blsgpu_verify_same_message      <- the whole of IBlsVerifier.verifySignatureSetsSameMessage: the `SameMessage` job's
  *                                      aggregateWithRandomness + verify of the aggregate, and the worker's retry of a
- *                                      failed job set by set (multithread/index.ts, jobItem.ts, worker.ts)
+ *                                      failed job set by set (multithread/index.ts, jobItem.ts, worker.ts); with
+ *                                      BLSGPU_SAME_BLOCK_CHECK the groups' aggregates are first batch-verified 1024 at
+ *                                      a time under one final exponentiation, as the worker batch-verifies the
+ *                                      aggregated sets of many `SameMessage` jobs (worker.ts:56)
+ *   blsgpu_same_message_blocks      <- how many such blocks a call of n_groups groups checks (pure host code)
  *   blsgpu_key_validate             <- PublicKey.fromBytes(pk, CoordType.affine, validate = true) for untrusted
  *                                      keys (state-transition/src/block/processDeposit.ts:56-64,
  *                                      beacon-node/test/spec/general/bls.ts:33-42)
@@ -55,7 +59,8 @@ extern "C" {
 
 /* Bumped when an existing entry point or struct changes.  Entry points added since 8, which leave every existing one
  * as it was and so keep the number: blsgpu_randomness_words, blsgpu_aggregate_with_randomness, blsgpu_awr_lanes,
- * blsgpu_verify_same_message, blsgpu_same_message_form. */
+ * blsgpu_verify_same_message, blsgpu_same_message_form, blsgpu_same_message_blocks (and the flag
+ * BLSGPU_SAME_BLOCK_CHECK of blsgpu_verify_same_message, which was refused before). */
 #define BLSGPU_ABI_VERSION 8
 
 /* blsgpu_batch.job_flags bits (reference VerifySignatureOpts, chain/bls/interface.ts:3-18) */
@@ -317,13 +322,17 @@ int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const u
 uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets);
 
 #define BLSGPU_SAME_LANE_FORMS 1u /* diagnostics / tests: take the large-call kernel forms whatever the size */
+/* (2u is not a flag: it stays refused) */
+#define BLSGPU_SAME_BLOCK_CHECK 4u /* check the groups' aggregates a block of 1024 groups at a time, see below */
 
 typedef struct blsgpu_same_message_stats {
   uint32_t groups_accepted; /* non-empty groups whose aggregate check held: every set 1 */
   uint32_t groups_retried;  /* non-empty groups verified set by set */
   uint32_t retry_sets;      /* their sets */
   uint32_t unique_messages; /* distinct messages over all groups of the call */
-  uint32_t form;            /* bit 0: group phase took the lane forms, bit 1: retry phase did (0 = cooperative) */
+  uint32_t form;            /* bit 0: group phase took the lane forms, bit 1: retry phase did (0 = cooperative);
+                               only with BLSGPU_SAME_BLOCK_CHECK: bit 2 (4) the block phase ran, bit 3 (8) some block
+                               failed and the per-group descent ran, bit 4 (16) the descent's checks took the lane forms */
   double device_ms;         /* host clock around the device work of the call */
 } blsgpu_same_message_stats;
 
@@ -344,7 +353,21 @@ typedef struct blsgpu_same_message_stats {
  * in a narrower stride) return BLSGPU_ERR_ARGS before anything is read or reaches the device, as does a table index
  * beyond the table; n_groups == 0 returns BLSGPU_OK.
  * Runs on device 0 beside verification calls: the signature decode and sum on the helper stream, the key sum and the
- * messages' hash_to_G2 on two helper streams of their own, joined before the checks. */
+ * messages' hash_to_G2 on two helper streams of their own, joined before the checks.
+ *
+ * flags: BLSGPU_SAME_LANE_FORMS and BLSGPU_SAME_BLOCK_CHECK, alone or together; any other bit is an unknown flag.
+ * BLSGPU_SAME_BLOCK_CHECK changes how the groups' checks are run, never an answer: set_result, group_result,
+ * groups_accepted, groups_retried, retry_sets and unique_messages are for every input what the call answers without
+ * the flag, and the error rules above hold unchanged.  The groups' Miller values are computed as without the flag.
+ * Then block b = groups [1024 b, min(n_groups, 1024 (b + 1))) (blsgpu_same_message_blocks counts them) is checked with
+ * one final exponentiation over the groups the aggregation accepted with a finite P_g:
+ *   FinalExp(prod_g MillerLoop(P_g, H(m_g)) * MillerLoop(-g1, sum_g S_g)) == 1
+ * which is the random-linear-combination equation over every set of the block under that set's own scalar r_k, so a
+ * block holding a set that does not verify passes with probability 2^-64, as a batch group of blsgpu_verify does.  The
+ * groups of a block that passes are accepted.  The groups of a block that fails are checked one by one from the Miller
+ * values already computed (the descent; a failed block with a single such group needs no second check), and the groups
+ * that fail that are verified set by set as without the flag.  stats.form bits 2 to 4 say which of this ran
+ * (DESIGN.md 4.4). */
 int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
                                const uint8_t* msgs /* [32 * n_groups] */, const uint8_t* pk_bytes,
                                const uint32_t* pk_index, const uint8_t* sigs, uint32_t sig_stride,
@@ -354,6 +377,10 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
 /* 0 = cooperative forms, 1 = lane forms for a phase of n_items pairings: at most 512 items (the default of option
  * "coop_max") are cooperative unless BLSGPU_SAME_LANE_FORMS is set.  Pure host code. */
 uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags);
+/* Blocks of groups blsgpu_verify_same_message checks under one final exponentiation each: 0 without
+ * BLSGPU_SAME_BLOCK_CHECK, else ceil(n_groups / 1024); block b is groups [1024 b, min(n_groups, 1024 (b + 1))).  1024 is
+ * the default of option "group_sets", taken as a constant.  Pure host code. */
+uint32_t blsgpu_same_message_blocks(uint32_t n_groups, uint32_t flags);
 
 /* KeyValidate of n untrusted pubkeys (pks[stride * i], pk_len 48 compressed or 96 uncompressed): status[i]
  * = 0 or BAD_ENCODING / POINT_NOT_ON_CURVE / PK_IS_INFINITY / POINT_NOT_IN_GROUP; out96 (nullable)

@@ -20,7 +20,7 @@ All of them run on the GPU through lodestar_amd.native.Context (there is no CPU 
 """
 import numpy as np
 
-from lodestar_amd.native import Context, code_name
+from lodestar_amd.native import SAME_BLOCK_CHECK, Context, code_name
 
 G1_INFINITY_48 = bytes([0xC0]) + bytes(47)
 G2_INFINITY_96 = bytes([0xC0]) + bytes(95)
@@ -206,10 +206,12 @@ def verify_signature_sets_same_message(ctx: Context, sets, message: bytes, seed=
     return [int(r) == 1 for r in res]
 
 
-def verify_same_message_groups(ctx: Context, groups, messages, seed=0):
+def verify_same_message_groups(ctx: Context, groups, messages, seed=0, block_check=False):
     """verifySignatureSetsSameMessage for many groups in ONE device call (Context.verify_same_message): groups[g] =
     [(pk96 or table index, signature bytes)] all signing messages[g]; a list with one list of bools per group, each
-    what verify_signature_sets_same_message answers for that group.  An empty group gives an empty list."""
+    what verify_signature_sets_same_message answers for that group.  An empty group gives an empty list.
+    block_check: the groups' aggregates are checked 1024 groups at a time under one final exponentiation
+    (native.SAME_BLOCK_CHECK) -- the same answers, fewer checks when most groups verify."""
     groups = [list(g) for g in groups]
     messages = [bytes(m)[:32].ljust(32, b"\0") for m in messages]
     if len(messages) != len(groups):
@@ -221,5 +223,6 @@ def verify_same_message_groups(ctx: Context, groups, messages, seed=0):
     if first[-1] == 0:
         pkb = b""  # no set at all: either key mode
     res, _, _ = ctx.verify_same_message(first, b"".join(messages), buf, pk_bytes=pkb, pk_index=pki, sig_len=sig_len,
-                                        sig_stride=stride, seed=seed)
+                                        sig_stride=stride, seed=seed,
+                                        flags=SAME_BLOCK_CHECK if block_check else 0)
     return [[int(r) == 1 for r in res[first[g]: first[g + 1]]] for g in range(len(groups))]

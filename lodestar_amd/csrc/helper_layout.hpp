@@ -119,6 +119,29 @@ struct SameRetry {
   }
 };
 
+// blsgpu_verify_same_message with BLSGPU_SAME_BLOCK_CHECK: what the block phase and the descent add, in buffers of
+// their own (hl::Same and hl::SameRetry are as without the flag).  Every region starts on a 256-byte boundary.
+//   block phase of nb blocks whose product tree starts `width` products wide per block, sized with the group phase's
+//   buffers:
+//     d_msmW (words): F_b | S_b | G_b (an Fp12, a Jacobian G2, MillerLoop(-g1, S_b) per block; stride nb) | T0 | T1 (the
+//                     tree's levels in turn: nb * width Fp12, and half of that)
+//     d_res (bytes):  any (the block has an included group) | ok (its check's verdict)
+//   descent over nl listed groups, grown after the block phase's synchronize:
+//     d_fkeep (words):   list | F | S | G (stride nl);  d_fbflags (bytes): ok
+struct SameBlocks {
+  size_t w_F, w_S, w_G, w_T0, w_T1, work_words, b_any, b_ok, bytes_total;
+  size_t d_list, d_F, d_S, d_G, descent_words, d_ok_bytes;
+  SameBlocks(size_t nb, size_t width, size_t nl) {
+    Carve w, b, d;
+    w_F = w.take(nb * kFp12 * 4) / 4, w_S = w.take(nb * kG2J * 4) / 4, w_G = w.take(nb * kFp12 * 4) / 4;
+    w_T0 = w.take(nb * width * kFp12 * 4) / 4, w_T1 = w.take(nb * (width / 2) * kFp12 * 4) / 4;
+    work_words = w.at / 4;
+    b_any = b.take(nb), b_ok = b.take(nb), bytes_total = b.at;
+    d_list = d.take(nl * 4) / 4, d_F = d.take(nl * kFp12 * 4) / 4, d_S = d.take(nl * kG2J * 4) / 4;
+    d_G = d.take(nl * kFp12 * 4) / 4, descent_words = d.at / 4, d_ok_bytes = nl;
+  }
+};
+
 // blsgpu_key_validate.  d_in: keys | out (96 bytes each) | status.
 struct KeyValidate {
   size_t keys, out, st, total;

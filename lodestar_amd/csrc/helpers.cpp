@@ -271,6 +271,11 @@ constexpr uint32_t kSameCoopMax = 512;
 uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags) {
   return (flags & BLSGPU_SAME_LANE_FORMS) || n_items > kSameCoopMax ? 1u : 0u;
 }
+// BLSGPU_SAME_BLOCK_CHECK: groups per block, the group_sets option's default as a constant (as kSameCoopMax above)
+static_assert(SAME_BLOCK_GROUPS == 1024, "include/blsgpu.h documents blocks of 1024 groups");
+uint32_t blsgpu_same_message_blocks(uint32_t n_groups, uint32_t flags) {
+  return flags & BLSGPU_SAME_BLOCK_CHECK ? n_groups / SAME_BLOCK_GROUPS + (n_groups % SAME_BLOCK_GROUPS ? 1u : 0u) : 0u;
+}
 namespace {
 // diagnostics (tools/bench_same_message.py): the three branches of the group phase on one stream
 inline bool same_serial() {
@@ -280,14 +285,14 @@ inline bool same_serial() {
   }();
   return on;
 }
-// Miller values and checks of one phase: item i < n_items pairs pk_aff[i] (W_G1A, stride n_items) with H(msg_idx[i]) when
-// include[i], and ok[i] = FinalExp(F_i * MillerLoop(-g1, S_i)) == 1 with S (W_G2J, stride n_items).  iota = 0, 1, ..,
-// n_items: one item per Miller chunk.  Cooperative form: k_miller_coop and k_group_check with its own Miller loop.
-// Lane form: the messages' stored lines (pm.lines), k_miller_acc6 (six lanes per pairing), MillerLoop(-g1, S) on one
-// lane per item and the final exponentiation on six (k_group_check6).
-void same_pairing_phase(const PipelineBuffers& pm, uint32_t n_items, const uint32_t* iota, uint32_t* pk_aff,
-                        uint8_t* include, const uint32_t* msg_idx, const uint32_t* S, uint32_t* F, uint32_t* Gs,
-                        uint8_t* ok, bool lane, hipStream_t s) {
+// Miller values and checks of one phase, in two halves.  Miller half: item i < n_items pairs pk_aff[i] (W_G1A, stride
+// n_items) with H(msg_idx[i]) when include[i], F_i (W_FP12, stride n_items).  iota = 0, 1, .., n_items: one item per
+// Miller chunk.  Check half: ok[i] = FinalExp(F_i * MillerLoop(-g1, S_i)) == 1 with S (W_G2J, stride n_items).
+// Cooperative form: k_miller_coop, and k_group_check with its own Miller loop.  Lane form: the messages' stored lines
+// (pm.lines), k_miller_acc6 (six lanes per pairing), MillerLoop(-g1, S) on one lane per item (into Gs) and the final
+// exponentiation on six (k_group_check6).
+void same_miller_half(const PipelineBuffers& pm, uint32_t n_items, const uint32_t* iota, uint32_t* pk_aff,
+                      uint8_t* include, const uint32_t* msg_idx, uint32_t* F, bool lane, hipStream_t s) {
   PipelineBuffers pb = pm;
   pb.n = n_items;
   pb.pk_aff = pk_aff;
@@ -297,14 +302,25 @@ void same_pairing_phase(const PipelineBuffers& pm, uint32_t n_items, const uint3
   pb.chunk_first = iota;
   pb.chunk_items = iota;
   pb.f_chunk = F;
-  if (!lane) {
+  if (!lane)
     launch_miller_coop(pb, false, s, false);
+  else
+    launch_miller_acc6(pb, false, s);
+}
+void same_check_half(uint32_t n_items, const uint32_t* S, const uint32_t* F, uint32_t* Gs, uint8_t* ok, bool lane,
+                     hipStream_t s) {
+  if (!lane) {
     launch_group_check(S, F, n_items, ok, s);
   } else {
-    launch_miller_acc6(pb, false, s);
     launch_group_sig_miller(S, n_items, Gs, s, false, true);
     launch_group_check6(F, Gs, n_items, ok, s);
   }
+}
+void same_pairing_phase(const PipelineBuffers& pm, uint32_t n_items, const uint32_t* iota, uint32_t* pk_aff,
+                        uint8_t* include, const uint32_t* msg_idx, const uint32_t* S, uint32_t* F, uint32_t* Gs,
+                        uint8_t* ok, bool lane, hipStream_t s) {
+  same_miller_half(pm, n_items, iota, pk_aff, include, msg_idx, F, lane, s);
+  same_check_half(n_items, S, F, Gs, ok, lane, s);
 }
 }  // namespace
 
@@ -314,7 +330,7 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
                                int8_t* set_result, int8_t* group_result, blsgpu_same_message_stats* stats) {
   if (!ctx || ctx->devs.empty() || !group_first || !msgs || !sigs || !sig_len || !set_result) return BLSGPU_ERR_ARGS;
   if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
-  if (sig_stride < 96 || (flags & ~BLSGPU_SAME_LANE_FORMS)) return BLSGPU_ERR_ARGS;
+  if (sig_stride < 96 || (flags & ~(BLSGPU_SAME_LANE_FORMS | BLSGPU_SAME_BLOCK_CHECK))) return BLSGPU_ERR_ARGS;
   if (n_groups == 0) {
     if (stats) memset(stats, 0, sizeof *stats);
     return BLSGPU_OK;
@@ -356,6 +372,14 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
       sl.d_bytes.ensure(l.bytes_total);
       sl.d_work.ensure(l.work_words);
       if (lane_g) sl.d_lines.ensure(l.lines_words);
+      // BLSGPU_SAME_BLOCK_CHECK: the block phase's buffers grow here too; the descent's, like the retry phase's, after
+      // the synchronize before it, and they are buffers no other phase uses
+      const uint32_t NB = blsgpu_same_message_blocks(G, flags);
+      const hl::SameBlocks lb(NB, NB ? same_block_tree_width(G) : 0, 0);
+      if (NB) {
+        sl.d_msmW.ensure(lb.work_words);
+        sl.d_res.ensure(lb.bytes_total);
+      }
       streams_used = true;
       uint8_t* din = sl.d_in.p;
       uint8_t* db = sl.d_bytes.p;
@@ -421,11 +445,67 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
         HIPCHK(hipStreamWaitEvent(s, d.same_ev[2], 0));
       }
       launch_same_group_items(ab, g_inv, g_pk_aff, g_inc, g_code, s);
-      same_pairing_phase(pm, G, d_iota, g_pk_aff, g_inc, d_gmsg, ab.sum_sig, g_F, g_G, g_ok, lane_g, s);
-      launch_same_group_results(ab.group_first, G, n, g_inc, g_code, g_ok, d_sres, d_gres, s);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(h_grp.data(), d_gres, G, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
+      std::vector<uint32_t> listed;  // (alive until the final synchronize: it is copied from)
+      if (!NB) {
+        same_pairing_phase(pm, G, d_iota, g_pk_aff, g_inc, d_gmsg, ab.sum_sig, g_F, g_G, g_ok, lane_g, s);
+        launch_same_group_results(ab.group_first, G, n, g_inc, g_code, g_ok, d_sres, d_gres, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_grp.data(), d_gres, G, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
+      } else {
+        // ---- block phase: F_b, S_b per block of groups and one check per block.  S_b needs the sums
+        // and the include flags only: it runs on sb, beside the Miller loops, and is joined into s before the check.
+        const bool lane_b = blsgpu_same_message_form(NB, flags) != 0;
+        uint32_t* bw = sl.d_msmW.p;
+        uint32_t* b_F = bw + lb.w_F;
+        uint32_t* b_S = bw + lb.w_S;
+        uint8_t* b_any = sl.d_res.p + lb.b_any;
+        uint8_t* b_ok = sl.d_res.p + lb.b_ok;
+        HIPCHK(hipEventRecord(d.same_ev[0], s));
+        if (!serial) HIPCHK(hipStreamWaitEvent(sb, d.same_ev[0], 0));
+        launch_same_block_sum(ab.sum_sig, g_inc, G, NB, b_S, b_any, sb);
+        HIPCHK(hipEventRecord(d.same_ev[1], sb));
+        same_miller_half(pm, G, d_iota, g_pk_aff, g_inc, d_gmsg, g_F, lane_g, s);
+        launch_same_block_prod(g_F, g_inc, G, NB, bw + lb.w_T0, bw + lb.w_T1, b_F, s);
+        if (!serial) HIPCHK(hipStreamWaitEvent(s, d.same_ev[1], 0));
+        same_check_half(NB, b_S, b_F, sl.d_msmW.p + lb.w_G, b_ok, lane_b, s);
+        launch_same_block_results(ab.group_first, G, n, g_inc, g_code, b_any, b_ok, d_sres, d_gres, s);
+        HIPCHK(hipGetLastError());
+        std::vector<uint8_t> h_blk(2 * (size_t)NB), h_inc(G);
+        HIPCHK(hipMemcpyAsync(h_blk.data(), b_any, NB, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_blk.data() + NB, b_ok, NB, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_inc.data(), g_inc, G, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_grp.data(), d_gres, G, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
+        st.form |= 4;
+        // ---- descent: the included groups of the failed blocks, each checked from its own F_g, S_g.  A failed block
+        // with one included group has its answer already: that group failed.
+        for (uint32_t b = 0; b < NB; b++) {
+          if (!h_blk[b] || h_blk[NB + b]) continue;
+          const uint32_t first = b * SAME_BLOCK_GROUPS, last = std::min<uint64_t>(G, (uint64_t)first + SAME_BLOCK_GROUPS);
+          const size_t before = listed.size();
+          for (uint32_t g = first; g < last; g++)
+            if (h_inc[g]) listed.push_back(g);
+          if (listed.size() - before == 1) listed.pop_back();
+        }
+        const uint32_t nl = (uint32_t)listed.size();
+        if (nl) {
+          const bool lane_d = blsgpu_same_message_form(nl, flags) != 0;
+          const hl::SameBlocks ld(NB, 0, nl);
+          sl.d_fkeep.ensure(ld.descent_words);
+          sl.d_fbflags.ensure(ld.d_ok_bytes);
+          uint32_t* dw = sl.d_fkeep.p;
+          uint8_t* l_ok = sl.d_fbflags.p;
+          HIPCHK(hipMemcpyAsync(dw + ld.d_list, listed.data(), (size_t)nl * 4, hipMemcpyHostToDevice, s));
+          launch_same_gather(g_F, ab.sum_sig, G, dw + ld.d_list, nl, dw + ld.d_F, dw + ld.d_S, s);
+          same_check_half(nl, dw + ld.d_S, dw + ld.d_F, dw + ld.d_G, l_ok, lane_d, s);
+          launch_same_descent_results(ab.group_first, G, n, dw + ld.d_list, nl, l_ok, d_sres, d_gres, s);
+          HIPCHK(hipGetLastError());
+          HIPCHK(hipMemcpyAsync(h_grp.data(), d_gres, G, hipMemcpyDeviceToHost, s));
+          HIPCHK(hipStreamSynchronize(s));
+          st.form |= lane_d ? 8 | 16 : 8;
+        }
+      }
       if (lane_g) st.form |= 1;
       // ---- retry phase: every set of a non-empty group whose check did not hold, on its own with r = 1
       std::vector<uint32_t> rlist, rmsg, riota;  // (alive until the final synchronize: they are copied from)

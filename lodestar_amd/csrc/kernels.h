@@ -288,6 +288,32 @@ void launch_same_group_results(const uint32_t* group_first, uint32_t n_groups, u
 // set_result[list[q]] = -code[q], or include[q] && ok[q]
 void launch_same_retry_results(const uint32_t* list, uint32_t n_retry, const uint8_t* include, const int8_t* code,
                                const uint8_t* ok, int8_t* set_result, hipStream_t s);
+// BLSGPU_SAME_BLOCK_CHECK: groups per block (the default of option "group_sets", as a constant: helper calls read no
+// option; blsgpu_same_message_blocks is the rule)
+#ifndef SAME_BLOCK_GROUPS
+#define SAME_BLOCK_GROUPS 1024u
+#endif
+// per block b of SAME_BLOCK_GROUPS groups: S_out (W_G2J, stride n_blocks) = sum S_g (stride n_groups) over its groups
+// with include[g], any[b] = whether it had one
+void launch_same_block_sum(const uint32_t* S, const uint8_t* include, uint32_t n_groups, uint32_t n_blocks,
+                           uint32_t* S_out, uint8_t* any, hipStream_t s);
+// F_out (W_FP12, stride n_blocks) = prod F_g (stride n_groups) over the same groups, as a product tree: the first level
+// has same_block_tree_width(n_groups) products per block (the least power of two that pairs up a block's groups), each
+// level half the one before; levels alternate between T0 (n_blocks * width Fp12) and T1 (half of that), F is not written
+uint32_t same_block_tree_width(uint32_t n_groups);
+void launch_same_block_prod(const uint32_t* F, const uint8_t* include, uint32_t n_groups, uint32_t n_blocks,
+                            uint32_t* T0, uint32_t* T1, uint32_t* F_out, hipStream_t s);
+// group_result[g] = -EMPTY_AGGREGATE, or include[g] && any[b] && ok[b] for g's block b; set_result[k] the same 1 / 0
+void launch_same_block_results(const uint32_t* group_first, uint32_t n_groups, uint32_t n_sets, const uint8_t* include,
+                               const int8_t* code, const uint8_t* any, const uint8_t* ok, int8_t* set_result,
+                               int8_t* group_result, hipStream_t s);
+// F_out / S_out (stride n_listed) = F / S (stride n_groups) of the groups list[0 .. n_listed)
+void launch_same_gather(const uint32_t* F, const uint32_t* S, uint32_t n_groups, const uint32_t* list,
+                        uint32_t n_listed, uint32_t* F_out, uint32_t* S_out, hipStream_t s);
+// group_result[list[q]] = ok[q], and set_result of every set of a listed group (list ascending)
+void launch_same_descent_results(const uint32_t* group_first, uint32_t n_groups, uint32_t n_sets, const uint32_t* list,
+                                 uint32_t n_listed, const uint8_t* ok, int8_t* set_result, int8_t* group_result,
+                                 hipStream_t s);
 // both sums' toBytes(): out_pk[out_pk_len * g] (48 compressed / 96), out_sig[out_sig_len * g] (96 compressed / 192),
 // zeros for a rejected or empty group; status[g] / first_bad[g] = the group's status and its rejected set's index
 void launch_awr_serialize(const AwrBuffers& a, uint8_t* out_pk, uint32_t out_pk_len, uint8_t* out_sig,

@@ -59,8 +59,10 @@ EXPORTED_SYMBOLS = [
     "blsgpu_awr_lanes",
     "blsgpu_verify_same_message",
     "blsgpu_same_message_form",
+    "blsgpu_same_message_blocks",
 ]
 SAME_LANE_FORMS = 1
+SAME_BLOCK_CHECK = 4  # BLSGPU_SAME_BLOCK_CHECK: one check per block of 1024 groups, then the descent
 ROOT_OBJECT = 0
 ROOT_ATTESTATION_DATA = 1
 
@@ -191,6 +193,8 @@ def load():
     lib.blsgpu_verify_same_message.restype = ctypes.c_int
     lib.blsgpu_same_message_form.argtypes = [u32, u32]
     lib.blsgpu_same_message_form.restype = u32
+    lib.blsgpu_same_message_blocks.argtypes = [u32, u32]
+    lib.blsgpu_same_message_blocks.restype = u32
     _lib = lib
     return lib
 
@@ -270,6 +274,12 @@ def same_message_form(n_items, flags=0):
     """The kernel forms blsgpu_verify_same_message gives a phase of n_items pairings (C-ABI blsgpu_same_message_form,
     pure host code): 0 = cooperative, 1 = lane forms."""
     return int(load().blsgpu_same_message_form(n_items, flags))
+
+
+def same_message_blocks(n_groups, flags=0):
+    """The blocks of groups blsgpu_verify_same_message checks under one final exponentiation each (C-ABI
+    blsgpu_same_message_blocks, pure host code): 0 without SAME_BLOCK_CHECK, else ceil(n_groups / 1024)."""
+    return int(load().blsgpu_same_message_blocks(n_groups, flags))
 
 
 def randomness_words(n, seed):

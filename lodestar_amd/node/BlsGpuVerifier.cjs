@@ -65,6 +65,7 @@ const SIG_STRIDE = 192;
 const JOB_BATCHABLE = 1;
 const JOB_URGENT = 2;
 const SAME_LANE_FORMS = 1; // BLSGPU_SAME_LANE_FORMS
+const SAME_BLOCK_CHECK = 4; // BLSGPU_SAME_BLOCK_CHECK
 
 // job codes (include/blsgpu.h enum blsgpu_code)
 const CODE_EMPTY_AGGREGATE = 9;
@@ -88,9 +89,11 @@ function jobError(code) {
 class BlsGpuVerifier {
   /**
    * @param {{devices?: number[], groupSets?: number, groupPolicy?: number, seed?: number,
-   *          fusedSameMessage?: boolean}} opts  fusedSameMessage (default false): a flush of same-message calls is ONE
-   *          addon.verifySameMessage call per pubkey mode (aggregation, the aggregates' checks and the per-set retry on
-   *          the device) instead of an aggregation call followed by verification jobs
+   *          fusedSameMessage?: boolean, sameMessageBlockCheck?: boolean}} opts  fusedSameMessage (default false): a
+   *          flush of same-message calls is ONE addon.verifySameMessage call per pubkey mode (aggregation, the
+   *          aggregates' checks and the per-set retry on the device) instead of an aggregation call followed by
+   *          verification jobs.  sameMessageBlockCheck (default false; only together with fusedSameMessage): that call
+   *          checks the aggregates 1024 at a time under one final exponentiation (SAME_BLOCK_CHECK), the same answers
    * @param {{metrics?: object, logger?: object}} modules
    */
   constructor(opts = {}, modules = {}) {
@@ -100,6 +103,7 @@ class BlsGpuVerifier {
     if (opts.groupPolicy) addon.setOption(this.ctx, "group_policy", opts.groupPolicy);
     this.seed = opts.seed || 0; // 0 = OS CSPRNG batch scalars; fixed only for comparison runs
     this.fusedSameMessage = !!opts.fusedSameMessage;
+    this.sameMessageBlockCheck = this.fusedSameMessage && !!opts.sameMessageBlockCheck;
     // verifyOnMainThread calls are latency-critical exceptions to the pool (the block proposer signature): they run on
     // the device's urgent lane.  The single-thread verifier sends every call that way and keeps the shared pipeline.
     this.urgentMainThread = true;
@@ -358,7 +362,8 @@ class BlsGpuVerifier {
   verifySameMessageFused(calls, groupFirst, pkBytes, pkIndex, sigs, sigLen) {
     const msgs = new Uint8Array(32 * calls.length);
     calls.forEach((c, ci) => msgs.set(c.message.subarray(0, 32), 32 * ci));
-    addon.verifySameMessage(this.ctx, groupFirst, msgs, pkBytes, pkIndex, sigs, sigLen, SIG_STRIDE, this.seed, 0).then(
+    const flags = this.sameMessageBlockCheck ? SAME_BLOCK_CHECK : 0;
+    addon.verifySameMessage(this.ctx, groupFirst, msgs, pkBytes, pkIndex, sigs, sigLen, SIG_STRIDE, this.seed, flags).then(
       (r) => {
         const m = this.metrics && this.metrics.blsThreadPool;
         calls.forEach((c, ci) => {
@@ -648,5 +653,6 @@ module.exports = {
   JOB_BATCHABLE,
   JOB_URGENT,
   SAME_LANE_FORMS,
+  SAME_BLOCK_CHECK,
   addon,
 };

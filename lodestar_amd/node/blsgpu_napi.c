@@ -38,6 +38,7 @@
  *       -> Promise<{setResult: Int8Array, groupResult: Int8Array, stats: {groupsAccepted, groupsRetried, retrySets,
  *                   uniqueMessages, form, deviceMs}}>
  *     blsgpu_verify_same_message as napi_create_async_work, the same lifetime rules as aggregateWithRandomness.
+ *     flags: BLSGPU_SAME_LANE_FORMS (1) and BLSGPU_SAME_BLOCK_CHECK (4); any other bit is a RangeError here.
  *   debugInject(what, skip, count)                                blsgpu_debug_inject (only with BLSGPU_FAULT_INJECTION=1)
  */
 #define NAPI_VERSION 6
@@ -845,7 +846,7 @@ static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
   napi_get_value_uint32(env, argv[9], &flags);
   /* shape checks on the host before anything is queued */
   const uint32_t* gfw = (const uint32_t*)gf;
-  int ok = n_gf >= 1 && stride >= 96 && !(flags & ~BLSGPU_SAME_LANE_FORMS) && gfw[0] == 0 &&
+  int ok = n_gf >= 1 && stride >= 96 && !(flags & ~(BLSGPU_SAME_LANE_FORMS | BLSGPU_SAME_BLOCK_CHECK)) && gfw[0] == 0 &&
            (pkb != NULL) != (pki != NULL) && seed >= 0 && seed < 9007199254740992.0 && n_msg == 32 * (n_gf - 1);
   for (size_t g = 0; ok && g + 1 < n_gf; g++) ok = gfw[g + 1] >= gfw[g];
   ok = ok && gfw[n_gf - 1] == n_len && n_len <= (1u << 20) && n_bytes >= (size_t)stride * n_len;

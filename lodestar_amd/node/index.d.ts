@@ -23,6 +23,10 @@ export type BlsGpuVerifierOpts = {
    * aggregate's pairing check and the per-set retry of the groups that fail, without leaving the device (default
    * false: an aggregation call, then verification jobs) */
   fusedSameMessage?: boolean;
+  /** true, together with fusedSameMessage: that call passes SAME_BLOCK_CHECK -- the aggregates are checked 1024 at a
+   * time under one final exponentiation, and only the groups of a block that fails one by one; the same answers
+   * (default false; ignored without fusedSameMessage) */
+  sameMessageBlockCheck?: boolean;
 };
 
 /** What addon.verifySameMessage resolves to (blsgpu_verify_same_message). */
@@ -36,7 +40,8 @@ export type SameMessageResult = {
     groupsRetried: number;
     retrySets: number;
     uniqueMessages: number;
-    /** bit 0: group phase took the lane forms, bit 1: retry phase did */
+    /** bit 0: group phase took the lane forms, bit 1: retry phase did; with SAME_BLOCK_CHECK bit 2: the block phase
+     * ran, bit 3: some block failed and the per-group descent ran, bit 4: the descent's checks took the lane forms */
     form: number;
     deviceMs: number;
   };
@@ -124,4 +129,6 @@ export declare const MAX_BUFFER_WAIT_MS: number;
 export declare const MAX_JOBS_CAN_ACCEPT_WORK: number;
 /** flags bit of addon.verifySameMessage: the large-call kernel forms whatever the size (diagnostics) */
 export declare const SAME_LANE_FORMS: number;
+/** flags bit of addon.verifySameMessage: one check per block of 1024 groups, then the descent (blsgpu.h) */
+export declare const SAME_BLOCK_CHECK: number;
 export declare const addon: Record<string, (...args: unknown[]) => unknown>;

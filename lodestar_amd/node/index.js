@@ -19,6 +19,7 @@ export const {
   MAX_BUFFERED_SIGS,
   MAX_BUFFER_WAIT_MS,
   SAME_LANE_FORMS,
+  SAME_BLOCK_CHECK,
   addon,
 } = impl;
 export default impl;

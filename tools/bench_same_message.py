@@ -9,16 +9,19 @@ the same library and the same sets, on one device, and prints one JSON line.
     128x128 bad 100% one such set in every group
 Per shape:
     fused      Context.verify_same_message
+    fused_blocks  the same call with native.SAME_BLOCK_CHECK: one pairing check per block of 1024 groups, the per-group
+               descent of a block that fails, then the per-set retry
     two_step   the existing method, unchanged code: Context.aggregate_with_randomness, then Context.verify_raw of the
                (P, message, S) of every accepted group as one-set batchable jobs, then Context.verify_raw of every set
                of the groups that were rejected or did not verify, as one-set batchable jobs
     serial     the fused call with its three branches on one stream (BLSGPU_SAME_SERIAL=1, read once per process: a
                child process times it)
-Both answers are compared set by set before anything is timed.  fused and two_step run in the same process, are warmed
-up `--warmup` times and timed `--calls` times (>= 20), alternately (one call of each per round), with a host clock
+All answers are compared set by set before anything is timed.  fused, fused_blocks and two_step run in the same process,
+are warmed up `--warmup` times and timed `--calls` times (>= 20), alternately (one call of each per round), with a host
+clock
 around the calls, which end in a stream synchronise; medians, minima and maxima are reported.
 
-    python tools/bench_same_message.py [--calls 30] [--warmup 5] [--out FILE]
+    python tools/bench_same_message.py [--calls 30] [--warmup 5] [--out FILE] [--no-serial]
 """
 import argparse
 import hashlib
@@ -35,6 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 N_SETS = 16384
+SAME_BLOCK_CHECK = 4  # native.SAME_BLOCK_CHECK
 # name, groups, sets per group, groups with one bad set
 SHAPES = [("128x128", 128, 128, 0), ("16384x1", 16384, 1, 0), ("128x128_bad_1pct", 128, 128, 1),
           ("128x128_bad_100pct", 128, 128, 128)]
@@ -84,6 +88,10 @@ def time_shape(ctx, n_groups, size, bad_groups, calls, warmup, fused_only):
     def fused():
         last["fused"] = ctx.verify_same_message(first, gmsgs, buf, pk_bytes=pkb, sig_len=sl, sig_stride=96, seed=0)
 
+    def fused_blocks():
+        last["blocks"] = ctx.verify_same_message(first, gmsgs, buf, pk_bytes=pkb, sig_len=sl, sig_stride=96, seed=0,
+                                                 flags=SAME_BLOCK_CHECK)
+
     def two_step():
         p, s, st, _ = ctx.aggregate_with_randomness(first, buf, pk_bytes=pkb, sig_len=sl, sig_stride=96, seed=0)
         good = [g for g in range(n_groups) if st[g] == 0]
@@ -113,13 +121,21 @@ def time_shape(ctx, n_groups, size, bad_groups, calls, warmup, fused_only):
            "unique_messages": st.unique_messages}
     legs = {"fused": fused}
     if not fused_only:
+        fused_blocks()
+        bres, bgres, bst = last["blocks"]
+        assert (bres == res).all() and (bgres == gres).all() and bst.retry_sets == st.retry_sets
+        out["form_blocks"] = bst.form
+        legs["fused_blocks"] = fused_blocks
         two_step()
         assert (last["two"] == want).all()
         legs["two_step"] = two_step
     out.update(timed(legs, calls, warmup))
     out["fused"]["device_ms_last"] = last["fused"][2].device_ms
     if not fused_only:
+        out["fused_blocks"]["device_ms_last"] = last["blocks"][2].device_ms
         out["fused_over_two_step"] = out["fused"]["median_ms"] / out["two_step"]["median_ms"]
+        out["fused_blocks_over_two_step"] = out["fused_blocks"]["median_ms"] / out["two_step"]["median_ms"]
+        out["fused_blocks_over_fused"] = out["fused_blocks"]["median_ms"] / out["fused"]["median_ms"]
     return out
 
 
@@ -129,6 +145,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--fused-only", action="store_true", help="time the fused call alone (the serial child)")
+    ap.add_argument("--no-serial", action="store_true", help="leave the serial child out")
     a = ap.parse_args()
     if a.calls < 20:
         ap.error("--calls must be at least 20")
@@ -140,7 +157,7 @@ def main():
                   for name, g, size, bad in SHAPES}
     finally:
         ctx.close()
-    if not a.fused_only:
+    if not a.fused_only and not a.no_serial:
         # the same fused calls with the three branches of the group phase on one stream, in a process of their own
         env = dict(os.environ, BLSGPU_SAME_SERIAL="1")
         child = subprocess.run([sys.executable, os.path.abspath(__file__), "--fused-only", "--calls", str(a.calls),
