@@ -32,6 +32,11 @@
  *                                      a time under one final exponentiation, as the worker batch-verifies the
  *                                      aggregated sets of many `SameMessage` jobs (worker.ts:56)
  *   blsgpu_same_message_blocks      <- how many such blocks a call of n_groups groups checks (pure host code)
+ *   blsgpu_aggregate_verify         <- blst-ts aggregateVerify(msgs, pks, sig), the consensus-spec AggregateVerify
+ *                                      (beacon-node/test/spec/general/bls.ts `aggregate_verify`): one aggregated
+ *                                      signature over (pubkey, message) pairs with a message per key, many such jobs
+ *                                      per call
+ *   blsgpu_aggregate_verify_form    <- which kernel forms such a call takes (pure host code)
  *   blsgpu_key_validate             <- PublicKey.fromBytes(pk, CoordType.affine, validate = true) for untrusted
  *                                      keys (state-transition/src/block/processDeposit.ts:56-64,
  *                                      beacon-node/test/spec/general/bls.ts:33-42)
@@ -60,7 +65,8 @@ extern "C" {
 /* Bumped when an existing entry point or struct changes.  Entry points added since 8, which leave every existing one
  * as it was and so keep the number: blsgpu_randomness_words, blsgpu_aggregate_with_randomness, blsgpu_awr_lanes,
  * blsgpu_verify_same_message, blsgpu_same_message_form, blsgpu_same_message_blocks (and the flag
- * BLSGPU_SAME_BLOCK_CHECK of blsgpu_verify_same_message, which was refused before). */
+ * BLSGPU_SAME_BLOCK_CHECK of blsgpu_verify_same_message, which was refused before), blsgpu_aggregate_verify,
+ * blsgpu_aggregate_verify_form (with blsgpu_aggregate_verify_stats and the BLSGPU_AV_* flags). */
 #define BLSGPU_ABI_VERSION 8
 
 /* blsgpu_batch.job_flags bits (reference VerifySignatureOpts, chain/bls/interface.ts:3-18) */
@@ -381,6 +387,60 @@ uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags);
  * BLSGPU_SAME_BLOCK_CHECK, else ceil(n_groups / 1024); block b is groups [1024 b, min(n_groups, 1024 (b + 1))).  1024 is
  * the default of option "group_sets", taken as a constant.  Pure host code. */
 uint32_t blsgpu_same_message_blocks(uint32_t n_groups, uint32_t flags);
+
+#define BLSGPU_AV_VALIDATE_KEYS 1u /* keys are untrusted: KeyValidate each (PublicKey.fromBytes(pk, validate = true)) */
+#define BLSGPU_AV_LANE_FORMS 2u    /* diagnostics / tests: take the large-call kernel forms whatever the size */
+
+typedef struct blsgpu_aggregate_verify_stats {
+  uint32_t pairs;           /* (key, message) pairs of the call */
+  uint32_t unique_messages; /* distinct messages hashed to G2 */
+  uint32_t miller_items;    /* Miller items accumulated: included pairs + one (-g1, sig) item per checked job */
+  uint32_t miller_chunks;   /* accumulators they were cut into */
+  uint32_t form;            /* 0 cooperative, 1 lane forms */
+  uint32_t jobs_checked;    /* jobs that reached the pairing check (no error, finite signature) */
+  double device_ms;         /* host clock around the device work */
+} blsgpu_aggregate_verify_stats;
+
+/* AggregateVerify for n_jobs jobs in one call: blst-ts aggregateVerify(msgs, pks, sig), the IETF AggregateVerify --
+ * one aggregated signature over (public key, message) pairs with a message of its own per key.  Job j owns pairs
+ * [job_first[j], job_first[j+1]); job_first is [n_jobs + 1], non-decreasing, starting at 0 (at most 1 << 20 pairs and
+ * 1 << 20 jobs per call).  Pair k is (key k, msgs[32 k]).  Job j has one signature, sigs[sig_stride * j], sig_len[j] =
+ * 96 (compressed) or 192 bytes, always subgroup-checked.
+ * Keys: exactly one of pk_bytes and pk_index is non-null.  Without BLSGPU_AV_VALIDATE_KEYS they are trusted, as
+ * everywhere in this ABI: pk_bytes[96 k] uncompressed affine (pk_len == 96; pk_len is not read in table mode), or
+ * device-table entry pk_index[k]; no subgroup check, and a key's error is BAD_ENCODING, POINT_NOT_ON_CURVE or
+ * PK_IS_INFINITY (an identity key).  With the flag, pk_bytes[pk_len k] holds 48-byte compressed or 96-byte encodings
+ * (pk_len 48 or 96) and each key goes through KeyValidate, which adds POINT_NOT_IN_GROUP; the flag together with
+ * pk_index is BLSGPU_ERR_ARGS.
+ * job_result[j] is -BLSGPU_EMPTY_AGGREGATE for a job with no pairs; else -code of the job's lowest-index rejected key,
+ * first_bad[j] (nullable) being that pair's index in the call; else -code of its signature (INVALID_SIZE, BAD_ENCODING,
+ * POINT_NOT_ON_CURVE, POINT_NOT_IN_GROUP); else 0 for an identity signature, as blsgpu_verify answers; else 1 or 0 by
+ *   FinalExp( prod_k MillerLoop(pk_k, H(m_k)) * MillerLoop(-g1, sig_j) ) == 1
+ * over the job's pairs.  first_bad[j] is 0xffffffff unless a key was rejected.  Messages may repeat within a job and
+ * across jobs (no distinctness is required, as in blst and in the proof-of-possession scheme); each distinct message
+ * of the call is hashed to G2 once.  Jobs never affect each other: every job has its own accumulators and its own
+ * final exponentiation.  There is no randomness and no seed.  A HIP failure returns BLSGPU_DEVICE_ERROR with nothing
+ * written: the call never writes a 0 it did not compute.
+ * Malformed arguments (a null pointer other than first_bad / stats, both or neither of pk_bytes / pk_index, a pk_len
+ * that does not fit the mode, sig_stride < 96, a 192-byte signature in a narrower stride, an unknown flag, a job_first
+ * not as above) return BLSGPU_ERR_ARGS before anything is read or reaches the device, as does a table index beyond the
+ * table; n_jobs == 0 returns BLSGPU_OK with zeroed stats.
+ * The signature is one more pair of its job, (-g1, sig), in the job's own Miller accumulators: a job of k pairs costs
+ * k + 1 Miller items with shared squarings and one final exponentiation.  stats (nullable): miller_items and
+ * miller_chunks count the items and accumulators of the jobs that reached the check.  Runs on device 0 beside
+ * verification calls: the signature decode on the helper stream, the keys and the messages' hash_to_G2 on two helper
+ * streams of their own, joined before the Miller loops. */
+int blsgpu_aggregate_verify(blsgpu_ctx* ctx, uint32_t n_jobs, const uint32_t* job_first /* [n_jobs + 1] */,
+                            const uint8_t* msgs /* [32 * n_pairs] */, const uint8_t* pk_bytes,
+                            uint32_t pk_len /* 48 or 96 */, const uint32_t* pk_index,
+                            const uint8_t* sigs /* [sig_stride * n_jobs] */, uint32_t sig_stride,
+                            const uint32_t* sig_len /* [n_jobs] */, uint32_t flags, int8_t* job_result /* [n_jobs] */,
+                            uint32_t* first_bad /* [n_jobs], nullable */,
+                            blsgpu_aggregate_verify_stats* stats /* nullable */);
+/* 0 = cooperative forms, 1 = lane forms for a call of n_items Miller items (the pairs of its non-empty jobs plus one
+ * item per such job): at most 512 items are cooperative unless BLSGPU_AV_LANE_FORMS is set, the rule of
+ * blsgpu_same_message_form.  Pure host code. */
+uint32_t blsgpu_aggregate_verify_form(uint32_t n_items, uint32_t flags);
 
 /* KeyValidate of n untrusted pubkeys (pks[stride * i], pk_len 48 compressed or 96 uncompressed): status[i]
  * = 0 or BAD_ENCODING / POINT_NOT_ON_CURVE / PK_IS_INFINITY / POINT_NOT_IN_GROUP; out96 (nullable)

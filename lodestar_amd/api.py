@@ -13,6 +13,9 @@ reference's own functions (same names in snake_case, same argument meaning and e
 * verify_signature_sets_same_message  IBlsVerifier.verifySignatureSetsSameMessage (chain/bls/interface.ts;
                                  multithread/index.ts + jobItem.ts: aggregate with randomness, verify the one set,
                                  retry every set on its own when that fails)
+* aggregate_verify               beacon-node/test/spec/general/bls.ts `aggregate_verify` (blst-ts aggregateVerify(msgs,
+                                 pks, sig) over untrusted keys, a message per key; any error -> False)
+* verify                         beacon-node/test/spec/general/bls.ts `verify` (one untrusted key; any error -> False)
 * process_deposit_signature      state-transition/src/block/processDeposit.ts:54-64 (KeyValidate + verify;
                                  any error -> False: the deposit is skipped, not rejected)
 
@@ -20,7 +23,7 @@ All of them run on the GPU through lodestar_amd.native.Context (there is no CPU 
 """
 import numpy as np
 
-from lodestar_amd.native import SAME_BLOCK_CHECK, Context, code_name
+from lodestar_amd.native import AV_LANE_FORMS, AV_VALIDATE_KEYS, SAME_BLOCK_CHECK, Context, code_name
 
 G1_INFINITY_48 = bytes([0xC0]) + bytes(47)
 G2_INFINITY_96 = bytes([0xC0]) + bytes(95)
@@ -100,6 +103,62 @@ def process_deposit_signature(ctx: Context, pubkey48: bytes, signing_root: bytes
     if st[0] != 0:
         return False
     return _one_job(ctx, keys, signing_root, signature) == 1
+
+
+def verify(ctx: Context, pubkey48: bytes, message: bytes, signature: bytes) -> bool:
+    """The spec runner's `verify`: one untrusted key, any error -> False (process_deposit_signature's rule)."""
+    return process_deposit_signature(ctx, pubkey48, message, signature)
+
+
+def aggregate_verify_jobs(ctx: Context, jobs, validate_keys=False, lane_forms=False):
+    """AggregateVerify for many jobs in ONE device call (Context.aggregate_verify): jobs = [(keys, messages,
+    signature)], one aggregated signature over the pairs (keys[i], messages[i]).  Over the whole call the keys are all
+    96-byte uncompressed, all 48-byte compressed (only with validate_keys) or all table indices (trusted).  A list
+    with one int per job: 1 valid, 0 invalid, -code (native.EMPTY_AGGREGATE for no pairs, else the lowest-index
+    rejected key's error, else the signature's)."""
+    jobs = [(list(k), [bytes(m)[:32].ljust(32, b"\0") for m in ms], bytes(s)) for k, ms, s in jobs]
+    if not jobs:
+        return []
+    if any(len(k) != len(ms) for k, ms, _ in jobs):
+        raise ValueError("one message per key")
+    keys = [k for ks, _, _ in jobs for k in ks]
+    table = [isinstance(k, (int, np.integer)) for k in keys]
+    if any(table) and not all(table):
+        raise ValueError("jobs mix table indices and pubkey bytes")
+    pkb = pki = None
+    pk_len = 96
+    if keys and table[0]:
+        pki = np.array([int(k) for k in keys], np.int64)
+    else:
+        keys = [bytes(k) for k in keys]
+        pk_len = len(keys[0]) if keys else 96
+        if pk_len not in ((48, 96) if validate_keys else (96,)) or any(len(k) != pk_len for k in keys):
+            raise ValueError("all keys 96-byte uncompressed, or all 48-byte compressed with validate_keys")
+        pkb = b"".join(keys)
+    sigs = [s for _, _, s in jobs]
+    stride = 192 if any(len(s) > 96 for s in sigs) else 96
+    # any other length is refused by the device with INVALID_SIZE; its bytes are not read
+    buf = b"".join(s[:stride].ljust(stride, b"\0") for s in sigs)
+    flags = (AV_VALIDATE_KEYS if validate_keys else 0) | (AV_LANE_FORMS if lane_forms else 0)
+    res, _, _ = ctx.aggregate_verify(np.cumsum([0] + [len(k) for k, _, _ in jobs]),
+                                     b"".join(m for _, ms, _ in jobs for m in ms), buf, pk_bytes=pkb, pk_len=pk_len,
+                                     pk_index=pki, sig_len=[len(s) for s in sigs], sig_stride=stride, flags=flags)
+    return [int(r) for r in res]
+
+
+def aggregate_verify(ctx: Context, pubkeys48, messages, signature: bytes) -> bool:
+    """The spec runner's `aggregate_verify`: blst-ts aggregateVerify over untrusted compressed keys, a message per
+    key.  Any error (a key KeyValidate rejects, a malformed signature), a length mismatch or no pairs -> False.
+    Messages are 32-byte signing roots, as everywhere in this library: another length is a ValueError, not an answer."""
+    pubkeys48 = [bytes(p) for p in pubkeys48]
+    messages = [bytes(m) for m in messages]
+    if not pubkeys48 or len(pubkeys48) != len(messages):
+        return False
+    if any(len(m) != 32 for m in messages):
+        raise ValueError("32-byte messages (signing roots) expected")
+    if any(len(p) != 48 for p in pubkeys48):
+        return False
+    return aggregate_verify_jobs(ctx, [(pubkeys48, messages, signature)], validate_keys=True)[0] == 1
 
 
 def process_deposit_signatures(ctx: Context, pubkeys48, signing_roots, signatures):

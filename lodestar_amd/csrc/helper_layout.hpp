@@ -142,6 +142,40 @@ struct SameBlocks {
   }
 };
 
+// blsgpu_aggregate_verify: J jobs over n pairs, U unique messages, C planned Miller chunks (aggverify_plan.hpp).
+// Items: pair k is item k, job j's (-g1, signature) item is item n + j, so the per-item arrays have stride T = n + J;
+// G2 columns: unique message u is column u, job j's signature column U + j, so the per-message arrays have stride
+// M = U + J.  `validate`: the keys go through KeyValidate first (kv96, b_kv).
+//   d_in:    job_first | sig_len | sigs | keys | unique messages | pair message indices | chunk_first | chunk_items |
+//            f_ranges (a job's chunk range) | kv96 (the validated keys, 96 bytes each)
+//   d_bytes: signature status | signature flags | KeyValidate status | pair code | message flags | include | checked |
+//            job code | verdict | job_result | first_bad
+//   d_work:  sig_aff | pk_aff | msg_idx | f_chunk | F | message branch (inv, h_aff, h_jac, h_norm, h_prep, h_q)
+//   d_lines: the Miller lines of the M columns (lane form)
+struct AggVerify {
+  size_t T, M, key_bytes;
+  size_t gf, len, sigs, keys, umsg, pmsg, cf, ci, fr, kv96, in_total;
+  size_t b_st, b_fl, b_kv, b_code, b_mf, b_inc, b_chk, b_jcode, b_ok, b_res, b_fb, bytes_total;
+  size_t w_pk_aff, w_midx, w_fchunk, w_F, w_minv, w_haff, w_hjac, w_hnorm, w_hprep, w_hq, work_words, lines_words;
+  AggVerify(size_t J, size_t n, size_t U, size_t C, size_t sig_stride, bool keys_are_bytes, size_t pk_len,
+            bool validate) {
+    Carve c, b, w{1};
+    T = n + J, M = U + J;
+    key_bytes = n * (keys_are_bytes ? pk_len : 4);
+    gf = c.take((J + 1) * 4), len = c.take(J * 4), sigs = c.take(J * sig_stride), keys = c.take(key_bytes);
+    umsg = c.take(U * 32), pmsg = c.take(n * 4), cf = c.take((C + 1) * 4), ci = c.take(T * 4);
+    fr = c.take(2 * J * 4), kv96 = c.take(validate ? n * 96 : 0), in_total = c.at;
+    b_st = b.take(J), b_fl = b.take(J), b_kv = b.take(validate ? n : 0), b_code = b.take(n), b_mf = b.take(M);
+    b_inc = b.take(T), b_chk = b.take(J), b_jcode = b.take(J), b_ok = b.take(J), b_res = b.take(J), b_fb = b.take(J * 4);
+    bytes_total = b.at;
+    w.take(J * kG2A);  // sig_aff, at 0
+    w_pk_aff = w.take(T * kG1A), w_midx = w.take(T), w_fchunk = w.take(T * kFp12), w_F = w.take(J * kFp12);
+    w_minv = w.take(M * kFp), w_haff = w.take(M * kG2A), w_hjac = w.take(M * kG2J), w_hnorm = w.take(M * kFp);
+    w_hprep = w.take(M * 14 * kFp), w_hq = w.take(M * 2 * kG2J);
+    work_words = w.end, lines_words = M * kMillerLineWords;
+  }
+};
+
 // blsgpu_key_validate.  d_in: keys | out (96 bytes each) | status.
 struct KeyValidate {
   size_t keys, out, st, total;

@@ -1,12 +1,14 @@
-// The synchronous helper calls of libblsgpu (include/blsgpu.h): aggregation, same-message verification, key
-// validation, signing roots and the debug ops.  Each runs start to finish on device 0 under Device::helper_mu, on
+// The synchronous helper calls of libblsgpu (include/blsgpu.h): aggregation, same-message verification, AggregateVerify,
+// key validation, signing roots and the debug ops.  Each runs start to finish on device 0 under Device::helper_mu, on
 // table_stream, in Device::helper's buffers; helper_call is the envelope they share and helper_layout.hpp says where
 // every field of their device arenas lies.  The asynchronous verification pipeline is runtime.cpp and pipeline.cpp.
+#include "aggverify_plan.hpp"
 #include "helper_layout.hpp"
 #include "runtime_internal.hpp"
 
 using namespace blsgpu_rt;
 namespace hl = helper_layout;
+namespace avp = aggverify_plan;
 
 static_assert(hl::kFp == W_FP && hl::kG1A == W_G1A && hl::kG1J == W_G1J && hl::kG2A == W_G2A && hl::kG2J == W_G2J &&
                   hl::kFp12 == W_FP12 && hl::kAwrTabWords == AWR_TAB_WORDS && hl::kMillerLineWords == kMillerLineWords,
@@ -570,6 +572,222 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
   if (rc == BLSGPU_OK) {  // results reach the caller only when every one of them was computed
     if (n) memcpy(set_result, h_set.data(), n);
     if (group_result) memcpy(group_result, h_grp.data(), G);
+    if (stats) *stats = st;
+  }
+  return rc;
+}
+
+// ---- batched AggregateVerify -----------------------------------------------------------------------------------
+// A job's signature is one more pair of the job, (-g1, sig): k pairs are k + 1 Miller items in the job's own
+// accumulators and one final exponentiation (aggverify_plan.hpp, k_aggverify.hip).
+uint32_t blsgpu_aggregate_verify_form(uint32_t n_items, uint32_t flags) {
+  return avp::form(n_items, (flags & BLSGPU_AV_LANE_FORMS) != 0);
+}
+
+int blsgpu_aggregate_verify(blsgpu_ctx* ctx, uint32_t n_jobs, const uint32_t* job_first, const uint8_t* msgs,
+                            const uint8_t* pk_bytes, uint32_t pk_len, const uint32_t* pk_index, const uint8_t* sigs,
+                            uint32_t sig_stride, const uint32_t* sig_len, uint32_t flags, int8_t* job_result,
+                            uint32_t* first_bad, blsgpu_aggregate_verify_stats* stats) {
+  if (!ctx || ctx->devs.empty() || !job_first || !msgs || !sigs || !sig_len || !job_result) return BLSGPU_ERR_ARGS;
+  if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
+  if (sig_stride < 96 || (flags & ~(BLSGPU_AV_VALIDATE_KEYS | BLSGPU_AV_LANE_FORMS))) return BLSGPU_ERR_ARGS;
+  const bool validate = (flags & BLSGPU_AV_VALIDATE_KEYS) != 0;
+  if (validate ? (!pk_bytes || (pk_len != 48 && pk_len != 96)) : (pk_bytes && pk_len != 96)) return BLSGPU_ERR_ARGS;
+  if (n_jobs == 0) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    return BLSGPU_OK;
+  }
+  if (n_jobs > (1u << 20) || job_first[0] != 0) return BLSGPU_ERR_ARGS;
+  for (uint32_t j = 0; j < n_jobs; j++)
+    if (job_first[j + 1] < job_first[j]) return BLSGPU_ERR_ARGS;
+  const uint32_t J = n_jobs, n = job_first[J];
+  if (n > (1u << 20)) return BLSGPU_ERR_ARGS;
+  if (sig_stride < 192)
+    for (uint32_t j = 0; j < J; j++)
+      if (sig_len[j] == 192) return BLSGPU_ERR_ARGS;
+  std::vector<int8_t> h_res(J);
+  std::vector<uint32_t> h_fb(J);
+  std::vector<uint8_t> h_chk(J);
+  blsgpu_aggregate_verify_stats st;
+  memset(&st, 0, sizeof st);
+  const int rc = helper_call(ctx, true, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    if (pk_index)
+      for (uint32_t k = 0; k < n; k++)
+        if (pk_index[k] >= d.table_n) return BLSGPU_ERR_ARGS;
+    // messages, deduplicated over the whole call: pair k signs unique message pmsg[k].  The call draws no randomness,
+    // so the index is keyed by a constant (the key only spreads the table's probes; equality is by memcmp).
+    std::vector<uint32_t> pmsg(n), uniq;
+    {
+      MsgIndex mi(n, 0xbb67ae8584caa73bull);
+      for (uint32_t k = 0; k < n; k++) pmsg[k] = mi.find_or_add(msgs, k, uniq);
+    }
+    const uint32_t U = (uint32_t)uniq.size();
+    // every non-empty job is planned: which of them the device rejects is known only after the decodes, and their
+    // items are switched off by the include bytes (one synchronize less than reading the status back first)
+    const avp::Counts planned = avp::count(job_first, J, nullptr, 1);
+    const bool lane = blsgpu_aggregate_verify_form(planned.items, flags) != 0;
+    const uint32_t kc = avp::chunk_items_for(job_first, J, lane ? 1 : 0, (flags & BLSGPU_AV_LANE_FORMS) != 0);
+    const avp::Plan plan = avp::build(job_first, J, nullptr, kc);
+    const uint32_t C = plan.n_chunks();
+    // jobs of few chunks: a lane per job multiplies its chunk values; else a wave per job
+    const bool lane_reduce = lane && (uint64_t)C <= (uint64_t)avp::kLaneReduceMax * planned.jobs;
+    st.pairs = n;
+    st.unique_messages = U;
+    st.form = lane ? 1 : 0;
+    bool streams_used = false;
+    try {
+      if (!d.same_st[0]) {
+        for (auto& e : d.same_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIPCHK(hipStreamCreateWithFlags(&d.same_st[1], hipStreamNonBlocking));
+        HIPCHK(hipStreamCreateWithFlags(&d.same_st[0], hipStreamNonBlocking));
+      }
+      const auto t0 = std::chrono::steady_clock::now();
+      hipStream_t sb = d.same_st[0], sc = d.same_st[1];
+      const hl::AggVerify l(J, n, U, C, sig_stride, pk_bytes != nullptr, pk_len, validate);
+      // every buffer grows here, while none of the three streams has work (each call ends with all of them synchronized)
+      sl.d_in.ensure(l.in_total);
+      sl.d_bytes.ensure(l.bytes_total);
+      sl.d_work.ensure(l.work_words);
+      if (lane) sl.d_lines.ensure(l.lines_words);
+      streams_used = true;
+      uint8_t* din = sl.d_in.p;
+      uint8_t* db = sl.d_bytes.p;
+      uint32_t* w = sl.d_work.p;
+      std::vector<uint8_t> umsgs((size_t)U * 32);
+      for (uint32_t u = 0; u < U; u++) memcpy(umsgs.data() + (size_t)u * 32, msgs + (size_t)uniq[u] * 32, 32);
+      HIPCHK(hipMemcpyAsync(din + l.gf, job_first, (size_t)(J + 1) * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(din + l.len, sig_len, (size_t)J * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(din + l.sigs, sigs, (size_t)J * sig_stride, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(din + l.fr, plan.f_ranges.data(), (size_t)2 * J * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(din + l.cf, plan.chunk_first.data(), (size_t)(C + 1) * 4, hipMemcpyHostToDevice, s));
+      if (!plan.chunk_items.empty())
+        HIPCHK(hipMemcpyAsync(din + l.ci, plan.chunk_items.data(), plan.chunk_items.size() * 4, hipMemcpyHostToDevice, s));
+      if (n) {
+        HIPCHK(hipMemcpyAsync(din + l.keys, pk_bytes ? (const void*)pk_bytes : (const void*)pk_index, l.key_bytes,
+                              hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(din + l.umsg, umsgs.data(), (size_t)U * 32, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(din + l.pmsg, pmsg.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+      }
+      PipelineBuffers pb{};  // the signature decode: one signature per job
+      pb.n = J;
+      pb.sigs = din + l.sigs;
+      pb.sig_len = reinterpret_cast<uint32_t*>(din + l.len);
+      pb.sig_stride = sig_stride;
+      pb.sig_aff = w;
+      pb.flags = db + l.b_fl;
+      pb.status = reinterpret_cast<int8_t*>(db + l.b_st);
+      PipelineBuffers pm{};  // the message branch: U hashed columns of the M = U + J
+      pm.umsgs = din + l.umsg;
+      pm.n_umsg = U;
+      pm.nm = (uint32_t)l.M;
+      pm.inv_buf = w + l.w_minv;
+      pm.h_aff = w + l.w_haff;
+      pm.h_jac = w + l.w_hjac;
+      pm.h_norm = w + l.w_hnorm;
+      pm.h_prep = w + l.w_hprep;
+      pm.h_q = w + l.w_hq;
+      pm.mflags = db + l.b_mf;
+      pm.lines = sl.d_lines.p;
+      AvBuffers av{};
+      av.n_pairs = n;
+      av.n_jobs = J;
+      av.n_items = (uint32_t)l.T;
+      av.n_umsg = U;
+      av.nm = (uint32_t)l.M;
+      av.job_first = reinterpret_cast<uint32_t*>(din + l.gf);
+      av.pk_bytes = !pk_bytes ? nullptr : validate ? din + l.kv96 : din + l.keys;
+      av.kv_status = validate ? reinterpret_cast<int8_t*>(db + l.b_kv) : nullptr;
+      av.pk_index = pk_bytes ? nullptr : reinterpret_cast<uint32_t*>(din + l.keys);
+      av.pk_table = d.table.p;
+      av.pk_table_n = d.table_n;
+      av.pair_msg = reinterpret_cast<uint32_t*>(din + l.pmsg);
+      av.sig_aff = pb.sig_aff;
+      av.sig_flags = pb.flags;
+      av.sig_status = pb.status;
+      av.pk_aff = w + l.w_pk_aff;
+      av.msg_idx = w + l.w_midx;
+      av.include = db + l.b_inc;
+      av.pair_code = reinterpret_cast<int8_t*>(db + l.b_code);
+      av.h_aff = pm.h_aff;
+      av.mflags = pm.mflags;
+      av.checked = db + l.b_chk;
+      av.job_code = reinterpret_cast<int8_t*>(db + l.b_jcode);
+      av.first_bad = reinterpret_cast<uint32_t*>(db + l.b_fb);
+      uint32_t* F = w + l.w_F;
+      uint8_t* d_ok = db + l.b_ok;
+      int8_t* d_res = reinterpret_cast<int8_t*>(db + l.b_res);
+      // ---- three branches from the input copy, joined into s
+      HIPCHK(hipEventRecord(d.same_ev[0], s));
+      HIPCHK(hipStreamWaitEvent(sb, d.same_ev[0], 0));
+      HIPCHK(hipStreamWaitEvent(sc, d.same_ev[0], 0));
+      // (a) signatures: decode + subgroup check (cooperative for small calls, as small verification runs)
+      launch_sig_decode(pb, J, s, J <= 4096, nullptr, false, true);
+      // (b) keys: KeyValidate when they are untrusted, then every pair's affine point and code
+      if (validate)
+        launch_key_validate(din + l.keys, n, pk_len, pk_len, din + l.kv96, reinterpret_cast<int8_t*>(db + l.b_kv), sb);
+      launch_av_pair_items(av, sb);
+      HIPCHK(hipEventRecord(d.same_ev[1], sb));
+      // (c) messages: H(m) affine, and in the lane form the Miller lines of those columns
+      launch_hash_to_g2(pm, sc, U <= 4096, false);
+      launch_h_affine(pm, sc);
+      if (lane) launch_miller_lines2(pm, sc);
+      HIPCHK(hipEventRecord(d.same_ev[2], sc));
+      HIPCHK(hipStreamWaitEvent(s, d.same_ev[1], 0));
+      HIPCHK(hipStreamWaitEvent(s, d.same_ev[2], 0));
+      launch_av_job_items(av, s);
+      PipelineBuffers px = pm;  // the Miller accumulation over the T items and the M columns
+      px.n = (uint32_t)l.T;
+      px.n_umsg = (uint32_t)l.M;
+      px.pk_aff = av.pk_aff;
+      px.include = av.include;
+      px.msg_idx = av.msg_idx;
+      px.n_chunks = C;
+      px.chunk_first = reinterpret_cast<uint32_t*>(din + l.cf);
+      px.chunk_items = reinterpret_cast<uint32_t*>(din + l.ci);
+      px.f_chunk = w + l.w_fchunk;
+      const uint32_t* d_fr = reinterpret_cast<uint32_t*>(din + l.fr);
+      if (!lane) {
+        launch_miller_coop(px, false, s, false);
+      } else {
+        // the signature columns' lines: columns U .. M - 1, addressed as a call of J columns in the same arrays
+        PipelineBuffers ps = pm;
+        ps.n_umsg = J;
+        ps.h_aff = pm.h_aff + U;
+        ps.mflags = pm.mflags + U;
+        ps.lines = pm.lines + U;
+        launch_miller_lines2(ps, s);
+        launch_miller_acc(px, false, s);
+      }
+      if (lane_reduce)
+        launch_av_reduce_lane(px.f_chunk, px.n, d_fr, J, F, s);
+      else
+        launch_group_reduce(px, d_fr, J, F, s);
+      launch_av_check(F, J, av.checked, d_ok, lane, s);
+      launch_av_results(J, av.job_code, av.checked, d_ok, d_res, s);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(h_res.data(), d_res, J, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(h_fb.data(), av.first_bad, (size_t)J * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(h_chk.data(), av.checked, J, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
+      st.device_ms = ms_since(t0);
+    } catch (HipError&) {
+      // no branch may outlive the call: the next helper call reuses, and may grow, the buffers they work on
+      if (streams_used) {
+        (void)hipStreamSynchronize(d.table_stream);
+        for (hipStream_t x : d.same_st)
+          if (x) (void)hipStreamSynchronize(x);
+      }
+      throw;
+    }
+    const avp::Counts done = avp::count(job_first, J, h_chk.data(), kc);
+    st.jobs_checked = done.jobs;
+    st.miller_items = done.items;
+    st.miller_chunks = done.chunks;
+    return BLSGPU_OK;
+  });
+  if (rc == BLSGPU_OK) {  // results reach the caller only when every one of them was computed
+    memcpy(job_result, h_res.data(), J);
+    if (first_bad) memcpy(first_bad, h_fb.data(), (size_t)J * 4);
     if (stats) *stats = st;
   }
   return rc;

@@ -314,6 +314,49 @@ void launch_same_gather(const uint32_t* F, const uint32_t* S, uint32_t n_groups,
 void launch_same_descent_results(const uint32_t* group_first, uint32_t n_groups, uint32_t n_sets, const uint32_t* list,
                                  uint32_t n_listed, const uint8_t* ok, int8_t* set_result, int8_t* group_result,
                                  hipStream_t s);
+// Batched AggregateVerify (k_aggverify.hip, blsgpu_aggregate_verify): job j owns pairs [job_first[j], job_first[j+1])
+// and one signature.  Items (stride n_items = n_pairs + n_jobs): pair k is item k, job j's (-g1, signature) item is
+// item n_pairs + j.  G2 columns (stride nm = n_umsg + n_jobs): unique message u is column u, job j's signature is
+// column n_umsg + j.
+struct AvBuffers {
+  uint32_t n_pairs, n_jobs, n_items, n_umsg, nm;
+  const uint32_t* job_first;
+  // keys: pk_bytes[96 k] (trusted uncompressed, or launch_key_validate's output with its status in kv_status), or
+  // table entry pk_index[k] when pk_bytes is null
+  const uint8_t* pk_bytes;
+  const int8_t* kv_status;  // null: the keys are trusted
+  const uint32_t* pk_index;
+  const uint32_t* pk_table;
+  uint32_t pk_table_n;
+  const uint32_t* pair_msg;  // [n_pairs]: the pair's unique message
+  // the jobs' signatures as launch_sig_decode left them (stride n_jobs)
+  const uint32_t* sig_aff;
+  const uint8_t* sig_flags;
+  const int8_t* sig_status;
+  uint32_t* pk_aff;    // W_G1A per item
+  uint32_t* msg_idx;   // [n_items]: the item's G2 column
+  uint8_t* include;    // [n_items]
+  int8_t* pair_code;   // [n_pairs]: the key's error
+  uint32_t* h_aff;     // W_G2A per column
+  uint8_t* mflags;     // [nm]
+  uint8_t* checked;    // [n_jobs]: no error and a finite signature: the job reaches the pairing check
+  int8_t* job_code;    // [n_jobs]: EMPTY_AGGREGATE, the lowest-index rejected key's code, else the signature's
+  uint32_t* first_bad; // [n_jobs]: that key's pair index, 0xffffffff when no key was rejected
+};
+// per pair: pk_aff, msg_idx, pair_code
+void launch_av_pair_items(const AvBuffers& a, hipStream_t s);
+// per job: job_code, first_bad, checked, the signature's G2 column and its flag, the signature item and the include
+// bytes of every item of the job (set for a checked job, cleared for every other)
+void launch_av_job_items(const AvBuffers& a, hipStream_t s);
+// F[j] (W_FP12, stride n_jobs) = prod f_chunk over chunks [f_ranges[2j], f_ranges[2j+1]) on one lane per job (one for
+// an empty range); launch_group_reduce is the wave-per-job form
+void launch_av_reduce_lane(const uint32_t* f_chunk, uint32_t stride, const uint32_t* f_ranges, uint32_t n_jobs,
+                           uint32_t* F, hipStream_t s);
+// ok[j] = checked[j] && FinalExp(F[j]) == 1: a cooperative workgroup per job, or (lane) six lanes per job
+void launch_av_check(const uint32_t* F, uint32_t n_jobs, const uint8_t* checked, uint8_t* ok, bool lane, hipStream_t s);
+// job_result[j] = -code[j], or checked[j] && ok[j]
+void launch_av_results(uint32_t n_jobs, const int8_t* code, const uint8_t* checked, const uint8_t* ok,
+                       int8_t* job_result, hipStream_t s);
 // both sums' toBytes(): out_pk[out_pk_len * g] (48 compressed / 96), out_sig[out_sig_len * g] (96 compressed / 192),
 // zeros for a rejected or empty group; status[g] / first_bad[g] = the group's status and its rejected set's index
 void launch_awr_serialize(const AwrBuffers& a, uint8_t* out_pk, uint32_t out_pk_len, uint8_t* out_sig,

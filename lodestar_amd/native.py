@@ -60,9 +60,14 @@ EXPORTED_SYMBOLS = [
     "blsgpu_verify_same_message",
     "blsgpu_same_message_form",
     "blsgpu_same_message_blocks",
+    "blsgpu_aggregate_verify",
+    "blsgpu_aggregate_verify_form",
 ]
 SAME_LANE_FORMS = 1
 SAME_BLOCK_CHECK = 4  # BLSGPU_SAME_BLOCK_CHECK: one check per block of 1024 groups, then the descent
+# blsgpu_aggregate_verify flags
+AV_VALIDATE_KEYS = 1  # the keys are untrusted: KeyValidate each
+AV_LANE_FORMS = 2  # diagnostics / tests: the large-call kernel forms whatever the size
 ROOT_OBJECT = 0
 ROOT_ATTESTATION_DATA = 1
 
@@ -111,6 +116,18 @@ class SameMessageStats(ctypes.Structure):
         ("retry_sets", ctypes.c_uint32),
         ("unique_messages", ctypes.c_uint32),
         ("form", ctypes.c_uint32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
+class AggregateVerifyStats(ctypes.Structure):
+    _fields_ = [
+        ("pairs", ctypes.c_uint32),
+        ("unique_messages", ctypes.c_uint32),
+        ("miller_items", ctypes.c_uint32),
+        ("miller_chunks", ctypes.c_uint32),
+        ("form", ctypes.c_uint32),
+        ("jobs_checked", ctypes.c_uint32),
         ("device_ms", ctypes.c_double),
     ]
 
@@ -195,6 +212,10 @@ def load():
     lib.blsgpu_same_message_form.restype = u32
     lib.blsgpu_same_message_blocks.argtypes = [u32, u32]
     lib.blsgpu_same_message_blocks.restype = u32
+    lib.blsgpu_aggregate_verify.argtypes = [vp, u32, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp]
+    lib.blsgpu_aggregate_verify.restype = ctypes.c_int
+    lib.blsgpu_aggregate_verify_form.argtypes = [u32, u32]
+    lib.blsgpu_aggregate_verify_form.restype = u32
     _lib = lib
     return lib
 
@@ -280,6 +301,13 @@ def same_message_blocks(n_groups, flags=0):
     """The blocks of groups blsgpu_verify_same_message checks under one final exponentiation each (C-ABI
     blsgpu_same_message_blocks, pure host code): 0 without SAME_BLOCK_CHECK, else ceil(n_groups / 1024)."""
     return int(load().blsgpu_same_message_blocks(n_groups, flags))
+
+
+def aggregate_verify_form(n_items, flags=0):
+    """The kernel forms blsgpu_aggregate_verify gives a call of n_items Miller items -- the pairs of its non-empty
+    jobs plus one item per such job (C-ABI blsgpu_aggregate_verify_form, pure host code): 0 = cooperative, 1 = lane
+    forms."""
+    return int(load().blsgpu_aggregate_verify_form(n_items, flags))
 
 
 def randomness_words(n, seed):
@@ -606,6 +634,60 @@ class Context:
         if rc != OK:
             raise RuntimeError(f"blsgpu_verify_same_message -> {code_name(rc)}")
         return res[:n], gres[:n_groups], st
+
+    def aggregate_verify(self, job_first, msgs, sigs, pk_bytes=None, pk_len=96, pk_index=None, sig_len=None,
+                         sig_stride=None, flags=0):
+        """AggregateVerify for many jobs in one device call (blsgpu_aggregate_verify): job j owns pairs [job_first[j],
+        job_first[j + 1]), pair k = (pk_bytes[pk_len k] or table entry pk_index[k], msgs[32 k]), and has the one
+        signature sigs[sig_stride * j] of sig_len[j] bytes (default: all sig_stride).  flags: AV_VALIDATE_KEYS (the
+        keys are untrusted, pk_len 48 or 96), AV_LANE_FORMS.  Returns (job_result int8 array: 1 / 0 / -code per job,
+        first_bad uint32 array: the call index of the job's rejected key or 0xffffffff, AggregateVerifyStats).
+        ValueError for a malformed layout, before the library is called; RuntimeError for a call-level failure."""
+        jf = np.ascontiguousarray(job_first, dtype=np.int64)
+        if jf.ndim != 1 or len(jf) == 0:
+            raise ValueError("job_first needs n_jobs + 1 >= 1 entries")
+        if jf[0] != 0 or (np.diff(jf) < 0).any():
+            raise ValueError("job_first must start at 0 and never decrease")
+        n_jobs, n = len(jf) - 1, int(jf[-1])
+        if n > AGG_MAX_SIGS:
+            raise ValueError(f"at most {AGG_MAX_SIGS} pairs per call")
+        # the signatures: one per job, laid out as one group of n_jobs signatures
+        buf, _, sl, stride = aggregate_layout(sigs, [0, n_jobs], sig_len, sig_stride)
+        if (pk_bytes is None) == (pk_index is None):
+            raise ValueError("exactly one of pk_bytes and pk_index")
+        m = _u8(msgs)
+        if len(m) != 32 * n:
+            raise ValueError(f"{n} pairs need {32 * n} message bytes, got {len(m)}")
+        pkb = pki = None
+        if pk_bytes is not None:
+            if pk_len not in ((48, 96) if flags & AV_VALIDATE_KEYS else (96,)):
+                raise ValueError("pk_len must be 96, or 48 / 96 with AV_VALIDATE_KEYS")
+            pkb = _u8(pk_bytes)
+            if len(pkb) != pk_len * n:
+                raise ValueError(f"{n} pairs need {pk_len * n} pubkey bytes, got {len(pkb)}")
+        else:
+            if flags & AV_VALIDATE_KEYS:
+                raise ValueError("AV_VALIDATE_KEYS needs pk_bytes: table entries are trusted")
+            idx = np.ascontiguousarray(pk_index, dtype=np.int64)
+            if idx.ndim != 1 or len(idx) != n:
+                raise ValueError(f"pk_index needs one entry per pair ({n})")
+            if n and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+                raise ValueError("pk_index entries must be table indices")
+            pki = idx.astype(np.uint32)
+        pad = lambda a, t: np.zeros(1, t) if a is not None and len(a) == 0 else a  # noqa: E731
+        m, buf, sl, pkb, pki = pad(m, np.uint8), pad(buf, np.uint8), pad(sl, np.uint32), pad(pkb, np.uint8), \
+            pad(pki, np.uint32)
+        jf = jf.astype(np.uint32)
+        res = np.zeros(max(n_jobs, 1), np.int8)
+        fb = np.full(max(n_jobs, 1), 0xFFFFFFFF, np.uint32)
+        st = AggregateVerifyStats()
+        rc = self._lib.blsgpu_aggregate_verify(
+            self.h, n_jobs, jf.ctypes.data, m.ctypes.data, None if pkb is None else pkb.ctypes.data, pk_len,
+            None if pki is None else pki.ctypes.data, buf.ctypes.data, stride, sl.ctypes.data, flags,
+            res.ctypes.data, fb.ctypes.data, ctypes.byref(st))
+        if rc != OK:
+            raise RuntimeError(f"blsgpu_aggregate_verify -> {code_name(rc)}")
+        return res[:n_jobs], fb[:n_jobs], st
 
     def key_validate(self, pks: bytes, pk_len: int):
         """KeyValidate on the GPU: (96-byte uncompressed keys, status int8 array)."""

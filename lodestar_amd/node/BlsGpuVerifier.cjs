@@ -66,6 +66,8 @@ const JOB_BATCHABLE = 1;
 const JOB_URGENT = 2;
 const SAME_LANE_FORMS = 1; // BLSGPU_SAME_LANE_FORMS
 const SAME_BLOCK_CHECK = 4; // BLSGPU_SAME_BLOCK_CHECK
+const AV_VALIDATE_KEYS = 1; // BLSGPU_AV_VALIDATE_KEYS
+const AV_LANE_FORMS = 2; // BLSGPU_AV_LANE_FORMS
 
 // job codes (include/blsgpu.h enum blsgpu_code)
 const CODE_EMPTY_AGGREGATE = 9;
@@ -303,6 +305,64 @@ class BlsGpuVerifier {
     // in-flight submissions and aggregation calls complete (the device finishes them) before the context is freed
     await Promise.allSettled(Array.from(this.inflight));
     addon.close(this.ctx);
+  }
+
+  /**
+   * AggregateVerify (blst-ts aggregateVerify(msgs, pks, sig)) for many jobs in ONE device call
+   * (addon.aggregateVerify): jobs = [{pubkeys, messages, signature}], one aggregated signature over the pairs
+   * (pubkeys[i], messages[i]), 32-byte messages.  Over the whole call the keys are all 96-byte uncompressed Uint8Arrays
+   * (trusted), all 48-byte compressed or all 96-byte ones with {validateKeys: true} (KeyValidate on the device), or all
+   * table indices (numbers; trusted).  Resolves to one number per job: 1 valid, 0 invalid, -code (9 for no pairs, else
+   * the lowest-index rejected key's blst code, else the signature's).  Rejects for a call-level failure.
+   */
+  aggregateVerifyJobs(jobs, opts = {}) {
+    if (this.closed) return Promise.reject(new QueueError({code: QUEUE_ABORTED}));
+    if (jobs.length === 0) return Promise.resolve([]);
+    const validate = !!opts.validateKeys;
+    let n = 0;
+    for (const j of jobs) {
+      if (j.pubkeys.length !== j.messages.length) throw new TypeError("BlsGpuVerifier: aggregateVerifyJobs needs one message per key");
+      n += j.pubkeys.length;
+    }
+    const first = jobs.find((j) => j.pubkeys.length > 0);
+    const table = first !== undefined && typeof first.pubkeys[0] === "number";
+    const pkLen = first === undefined || table ? 96 : first.pubkeys[0].length;
+    if (table ? validate : !(pkLen === 96 || (validate && pkLen === 48)))
+      throw new TypeError("BlsGpuVerifier: aggregateVerifyJobs keys are 96-byte, 48-byte with validateKeys, or table indices without it");
+    const jobFirst = new Uint32Array(jobs.length + 1);
+    const msgs = new Uint8Array(32 * n);
+    const sigs = new Uint8Array(SIG_STRIDE * jobs.length);
+    const sigLen = new Uint32Array(jobs.length);
+    const pkIndex = table ? new Uint32Array(n) : null;
+    const pkBytes = table ? null : new Uint8Array(pkLen * n);
+    let k = 0;
+    jobs.forEach((j, ji) => {
+      jobFirst[ji] = k;
+      sigLen[ji] = j.signature.length; // 96 / 192, anything else -> BLST_INVALID_SIZE
+      sigs.set(j.signature.subarray(0, Math.min(j.signature.length, SIG_STRIDE)), SIG_STRIDE * ji);
+      j.pubkeys.forEach((p, i) => {
+        if (table ? typeof p !== "number" : typeof p === "number" || p.length !== pkLen)
+          throw new TypeError("BlsGpuVerifier: aggregateVerifyJobs keys must all be of one kind and length");
+        if (j.messages[i].length !== 32) throw new TypeError("BlsGpuVerifier: aggregateVerifyJobs messages are 32 bytes");
+        if (table) pkIndex[k] = p;
+        else pkBytes.set(p, pkLen * k);
+        msgs.set(j.messages[i], 32 * k);
+        k++;
+      });
+    });
+    jobFirst[jobs.length] = k;
+    const p = addon
+      .aggregateVerify(this.ctx, jobFirst, msgs, pkBytes, pkLen, pkIndex, sigs, sigLen, SIG_STRIDE, validate ? AV_VALIDATE_KEYS : 0)
+      .then(
+        (r) => Array.from(r.jobResult),
+        (err) => {
+          throw err.code === QUEUE_ABORTED ? new QueueError({code: QUEUE_ABORTED}) : err;
+        }
+      );
+    // close() waits for it: the device finishes the call before the context is freed
+    this.inflight.add(p);
+    p.finally(() => this.inflight.delete(p)).catch(() => {});
+    return p;
   }
 
   // ------------------------------------------------------------------------------------ internals
@@ -639,12 +699,30 @@ async function ethFastAggregateVerify(verifier, pubkeys48, message, signature) {
   return fastAggregateVerify(verifier, pubkeys48, message, signature);
 }
 
+/**
+ * aggregate_verify of the spec runner (beacon-node/test/spec/general/bls.ts): blst-ts aggregateVerify(msgs, pks, sig)
+ * over untrusted 48-byte keys, a message per key; any error, a length mismatch or no pairs -> false.
+ */
+async function aggregateVerify(verifier, pubkeys48, messages, signature) {
+  try {
+    if (pubkeys48.length === 0 || pubkeys48.length !== messages.length) return false;
+    if (pubkeys48.some((p) => p.length !== 48)) return false;
+    const r = await verifier.aggregateVerifyJobs([{pubkeys: pubkeys48, messages, signature}], {validateKeys: true});
+    return r[0] === 1;
+  } catch (e) {
+    return false;
+  }
+}
+
 module.exports = {
   BlsGpuVerifier,
   BlsGpuSingleThreadVerifier,
   verifySignatureSet,
   fastAggregateVerify,
   ethFastAggregateVerify,
+  aggregateVerify,
+  AV_VALIDATE_KEYS,
+  AV_LANE_FORMS,
   QueueError,
   SignatureSetType,
   MAX_BUFFERED_SIGS,

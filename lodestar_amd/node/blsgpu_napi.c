@@ -39,6 +39,13 @@
  *                   uniqueMessages, form, deviceMs}}>
  *     blsgpu_verify_same_message as napi_create_async_work, the same lifetime rules as aggregateWithRandomness.
  *     flags: BLSGPU_SAME_LANE_FORMS (1) and BLSGPU_SAME_BLOCK_CHECK (4); any other bit is a RangeError here.
+ *   aggregateVerify(ctx, jobFirst: Uint32Array, msgs: Uint8Array (32 bytes per pair), pkBytes: Uint8Array | null, pkLen,
+ *                   pkIndex: Uint32Array | null, sigs: Uint8Array (one per job), sigLen: Uint32Array, sigStride, flags)
+ *       -> Promise<{jobResult: Int8Array, firstBad: Uint32Array, stats: {pairs, uniqueMessages, millerItems,
+ *                   millerChunks, form, jobsChecked, deviceMs}}>
+ *     blsgpu_aggregate_verify as napi_create_async_work, the same lifetime rules as verifySameMessage.
+ *     flags: BLSGPU_AV_VALIDATE_KEYS (1, pkBytes of pkLen 48 or 96) and BLSGPU_AV_LANE_FORMS (2); any other bit, and
+ *     array sizes that do not fit jobFirst, are a RangeError here.
  *   debugInject(what, skip, count)                                blsgpu_debug_inject (only with BLSGPU_FAULT_INJECTION=1)
  */
 #define NAPI_VERSION 6
@@ -895,6 +902,161 @@ static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* aggregateVerify: one blsgpu_aggregate_verify call as async work (lifetimes as verifySameMessage: every input is
+ * copied before the call returns, the outputs are the call's own until its completion on the main thread, and the
+ * context stays open while the call is pending -- close() waits for agg_pending) */
+typedef struct {
+  CtxBox* box;
+  uint32_t n_jobs, pk_len, stride, flags;
+  uint32_t* job_first;
+  uint8_t* msgs;
+  uint8_t* pk_bytes;
+  uint32_t* pk_index;
+  uint32_t* sig_len;
+  uint8_t* sigs;
+  int8_t* job_result;
+  uint32_t* first_bad;
+  blsgpu_aggregate_verify_stats stats;
+  int rc;
+  napi_deferred deferred;
+  napi_async_work work;
+} AvCall;
+
+static void av_free(AvCall* a) {
+  free(a->job_first);
+  free(a->msgs);
+  free(a->pk_bytes);
+  free(a->pk_index);
+  free(a->sig_len);
+  free(a->sigs);
+  free(a->job_result);
+  free(a->first_bad);
+  free(a);
+}
+
+/* libuv worker thread */
+static void av_execute(napi_env env, void* data) {
+  (void)env;
+  AvCall* a = (AvCall*)data;
+  a->rc = blsgpu_aggregate_verify(a->box->ctx, a->n_jobs, a->job_first, a->msgs, a->pk_bytes, a->pk_len, a->pk_index,
+                                  a->sigs, a->stride, a->sig_len, a->flags, a->job_result, a->first_bad, &a->stats);
+}
+
+/* JS main thread */
+static void av_complete(napi_env env, napi_status st, void* data) {
+  AvCall* a = (AvCall*)data;
+  a->box->agg_pending--;
+  if (st != napi_ok || a->rc != BLSGPU_OK) {
+    const char* name = blsgpu_code_name(st != napi_ok ? BLSGPU_ERR_CLOSED : a->rc);
+    napi_value msg, code, err;
+    napi_create_string_utf8(env, name ? name : "BLSGPU_DEVICE_ERROR", NAPI_AUTO_LENGTH, &msg);
+    napi_create_string_utf8(env, name ? name : "BLSGPU_DEVICE_ERROR", NAPI_AUTO_LENGTH, &code);
+    napi_create_error(env, code, msg, &err);
+    napi_reject_deferred(env, a->deferred, err);
+  } else {
+    napi_value out, stats, ms;
+    napi_create_object(env, &out);
+    napi_set_named_property(env, out, "jobResult", copy_out(env, napi_int8_array, a->job_result, a->n_jobs, 1));
+    napi_set_named_property(env, out, "firstBad", copy_out(env, napi_uint32_array, a->first_bad, a->n_jobs, 4));
+    napi_create_object(env, &stats);
+    set_u32(env, stats, "pairs", a->stats.pairs);
+    set_u32(env, stats, "uniqueMessages", a->stats.unique_messages);
+    set_u32(env, stats, "millerItems", a->stats.miller_items);
+    set_u32(env, stats, "millerChunks", a->stats.miller_chunks);
+    set_u32(env, stats, "form", a->stats.form);
+    set_u32(env, stats, "jobsChecked", a->stats.jobs_checked);
+    napi_create_double(env, a->stats.device_ms, &ms);
+    napi_set_named_property(env, stats, "deviceMs", ms);
+    napi_set_named_property(env, out, "stats", stats);
+    napi_resolve_deferred(env, a->deferred, out);
+  }
+  napi_delete_async_work(env, a->work);
+  av_free(a);
+}
+
+static napi_value AggregateVerify(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value argv[10];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 10) {
+    napi_throw_type_error(env, NULL,
+                          "aggregateVerify(ctx, jobFirst, msgs, pkBytes, pkLen, pkIndex, sigs, sigLen, sigStride, flags)");
+    return NULL;
+  }
+  CtxBox* box = get_open_box(env, argv[0]);
+  if (!box) return NULL;
+  size_t n_jf = 0, n_msg = 0, n_pkb = 0, n_pki = 0, n_bytes = 0, n_len = 0;
+  void *jf = NULL, *msgs = NULL, *pkb = NULL, *pki = NULL, *sigs = NULL, *slen = NULL;
+  if (opt_typed(env, argv[1], napi_uint32_array, &jf, &n_jf) || !jf ||
+      opt_typed(env, argv[2], napi_uint8_array, &msgs, &n_msg) || !msgs ||
+      opt_typed(env, argv[3], napi_uint8_array, &pkb, &n_pkb) ||
+      opt_typed(env, argv[5], napi_uint32_array, &pki, &n_pki) ||
+      opt_typed(env, argv[6], napi_uint8_array, &sigs, &n_bytes) || !sigs ||
+      opt_typed(env, argv[7], napi_uint32_array, &slen, &n_len) || !slen) {
+    napi_throw_type_error(env, NULL,
+                          "aggregateVerify: jobFirst, pkIndex, sigLen Uint32Array; msgs, pkBytes, sigs Uint8Array");
+    return NULL;
+  }
+  uint32_t pk_len = 0, stride = 0, flags = 0;
+  napi_get_value_uint32(env, argv[4], &pk_len);
+  napi_get_value_uint32(env, argv[8], &stride);
+  napi_get_value_uint32(env, argv[9], &flags);
+  /* shape checks on the host before anything is queued */
+  const uint32_t* jfw = (const uint32_t*)jf;
+  const int validate = (flags & BLSGPU_AV_VALIDATE_KEYS) != 0;
+  int ok = n_jf >= 1 && stride >= 96 && !(flags & ~(BLSGPU_AV_VALIDATE_KEYS | BLSGPU_AV_LANE_FORMS)) && jfw[0] == 0 &&
+           (pkb != NULL) != (pki != NULL) && n_len == n_jf - 1 && n_len <= (1u << 20) &&
+           n_bytes >= (size_t)stride * n_len;
+  for (size_t j = 0; ok && j + 1 < n_jf; j++) ok = jfw[j + 1] >= jfw[j];
+  const size_t n_pairs = ok ? jfw[n_jf - 1] : 0;
+  ok = ok && n_pairs <= (1u << 20) && n_msg == 32 * n_pairs;
+  if (ok && pkb)
+    ok = (validate ? (pk_len == 48 || pk_len == 96) : pk_len == 96) && n_pkb == (size_t)pk_len * n_pairs;
+  else if (ok)
+    ok = !validate && n_pki == n_pairs;
+  for (size_t k = 0; ok && stride < 192 && k < n_len; k++) ok = ((const uint32_t*)slen)[k] != 192;
+  if (!ok) {
+    napi_throw_range_error(env, "BLSGPU_ERR_ARGS", "aggregateVerify: inconsistent array sizes");
+    return NULL;
+  }
+  AvCall* a = (AvCall*)calloc(1, sizeof(AvCall));
+  if (!a) {
+    napi_throw_error(env, NULL, "aggregateVerify: could not queue the call");
+    return NULL;
+  }
+  a->box = box;
+  a->n_jobs = (uint32_t)n_jf - 1;
+  a->pk_len = pk_len;
+  a->stride = stride;
+  a->flags = flags;
+  a->job_first = (uint32_t*)dup_bytes(jf, n_jf * 4);
+  a->msgs = (uint8_t*)dup_bytes(msgs, n_msg);
+  if (pkb) a->pk_bytes = (uint8_t*)dup_bytes(pkb, n_pkb);
+  if (pki) a->pk_index = (uint32_t*)dup_bytes(pki, n_pki * 4);
+  a->sig_len = (uint32_t*)dup_bytes(slen, n_len * 4);
+  a->sigs = (uint8_t*)dup_bytes(sigs, (size_t)stride * n_len);
+  a->job_result = (int8_t*)calloc((size_t)a->n_jobs + 1, 1);
+  a->first_bad = (uint32_t*)calloc((size_t)a->n_jobs + 1, 4);
+  napi_value promise, name;
+  if (!a->job_first || !a->msgs || (!a->pk_bytes && !a->pk_index) || !a->sig_len || !a->sigs || !a->job_result ||
+      !a->first_bad || napi_create_promise(env, &a->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "blsgpu_aggregate_verify", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, NULL, name, av_execute, av_complete, a, &a->work) != napi_ok) {
+    av_free(a);
+    napi_throw_error(env, NULL, "aggregateVerify: could not queue the call");
+    return NULL;
+  }
+  box->agg_pending++;
+  if (napi_queue_async_work(env, a->work) != napi_ok) {
+    box->agg_pending--;
+    napi_delete_async_work(env, a->work);
+    av_free(a);
+    napi_throw_error(env, NULL, "aggregateVerify: could not queue the call");
+    return NULL;
+  }
+  return promise;
+}
+
 /* debugInject(what, skip, count): blsgpu_debug_inject (test hook; BLSGPU_INJECT_ENTROPY 1, BLSGPU_INJECT_DEVICE 2) */
 static napi_value DebugInject(napi_env env, napi_callback_info info) {
   size_t argc = 3;
@@ -929,6 +1091,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
       {"aggregateSignatures", NULL, AggregateSignatures, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"aggregateWithRandomness", NULL, AggregateWithRandomness, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"verifySameMessage", NULL, VerifySameMessage, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
+      {"aggregateVerify", NULL, AggregateVerify, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   /* the fault-injection test hook is exported, by its own definition, only to processes started with

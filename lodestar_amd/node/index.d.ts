@@ -47,6 +47,31 @@ export type SameMessageResult = {
   };
 };
 
+/** One job of BlsGpuVerifier.aggregateVerifyJobs: pubkeys[i] signs messages[i] under the one aggregated signature. */
+export type AggregateVerifyJob = {
+  pubkeys: Uint8Array[] | number[];
+  messages: Uint8Array[];
+  signature: Uint8Array;
+};
+
+/** What addon.aggregateVerify resolves to (blsgpu_aggregate_verify). */
+export type AggregateVerifyResult = {
+  /** per job: 1 valid, 0 invalid, -code rejected */
+  jobResult: Int8Array;
+  /** per job: the call index of its lowest-index rejected key, 0xffffffff when none */
+  firstBad: Uint32Array;
+  stats: {
+    pairs: number;
+    uniqueMessages: number;
+    millerItems: number;
+    millerChunks: number;
+    /** 0 cooperative, 1 lane forms */
+    form: number;
+    jobsChecked: number;
+    deviceMs: number;
+  };
+};
+
 export type BlsGpuVerifierModules = {
   metrics?: unknown | null;
   logger?: unknown;
@@ -95,6 +120,13 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
     groups: Uint8Array[][],
     opts?: {validate?: boolean; compressed?: boolean}
   ): Promise<Array<Uint8Array | Error>>;
+  /** AggregateVerify (blst-ts aggregateVerify(msgs, pks, sig)) for many jobs in one device call, off the main thread:
+   * one aggregated signature per job over the pairs (pubkeys[i], messages[i]), 32-byte messages.  Over the whole call
+   * the keys are all 96-byte uncompressed (trusted), all 48- or all 96-byte with validateKeys (KeyValidate on the
+   * device), or all table indices (numbers; trusted).  One number per job: 1 valid, 0 invalid, -code (9 for no pairs,
+   * else the lowest-index rejected key's blst code, else the signature's).  Rejects only for a call-level failure or
+   * once closed (QUEUE_ERROR_QUEUE_ABORTED). */
+  aggregateVerifyJobs(jobs: AggregateVerifyJob[], opts?: {validateKeys?: boolean}): Promise<number[]>;
   /** IBlsVerifier.close: rejects buffered jobs with QUEUE_ERROR_QUEUE_ABORTED, waits for in-flight submissions and
    * aggregation calls, then frees the devices. */
   close(): Promise<void>;
@@ -122,6 +154,18 @@ export declare function ethFastAggregateVerify(
   message: Uint8Array,
   signature: Uint8Array
 ): Promise<boolean>;
+
+/** aggregate_verify of the spec runner: untrusted 48-byte keys, a message per key; any error, a length mismatch or no
+ * pairs resolves to false. */
+export declare function aggregateVerify(
+  verifier: BlsGpuVerifier,
+  pubkeys48: Uint8Array[],
+  messages: Uint8Array[],
+  signature: Uint8Array
+): Promise<boolean>;
+/** flags bits of addon.aggregateVerify: KeyValidate every key / the large-call kernel forms whatever the size */
+export declare const AV_VALIDATE_KEYS: number;
+export declare const AV_LANE_FORMS: number;
 
 export declare const SignatureSetType: {single: "single"; aggregate: "aggregate"};
 export declare const MAX_BUFFERED_SIGS: number;

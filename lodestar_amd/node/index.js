@@ -14,6 +14,9 @@ export const {
   verifySignatureSet,
   fastAggregateVerify,
   ethFastAggregateVerify,
+  aggregateVerify,
+  AV_VALIDATE_KEYS,
+  AV_LANE_FORMS,
   QueueError,
   SignatureSetType,
   MAX_BUFFERED_SIGS,
