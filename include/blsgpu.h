@@ -32,6 +32,12 @@
  *                                      a time under one final exponentiation, as the worker batch-verifies the
  *                                      aggregated sets of many `SameMessage` jobs (worker.ts:56)
  *   blsgpu_same_message_blocks      <- how many such blocks a call of n_groups groups checks (pure host code)
+ *   blsgpu_verify_same_message_agg  <- the same, and what the gossip handler does with the attestations that passed:
+ *                                      attestationPool.add folds each into the pool's aggregate of its AttestationData
+ *                                      (Signature.aggregate([aggregate.signature,
+ *                                      signatureFromBytesNoCheck(att.signature)]), opPools/attestationPool.ts); the call returns each group's sum over the sets
+ *                                      that verified, so the pool folds a group in with one G2 addition
+ *   blsgpu_same_message_agg_lanes   <- lanes per group of that sum (pure host code)
  *   blsgpu_aggregate_verify         <- blst-ts aggregateVerify(msgs, pks, sig), the consensus-spec AggregateVerify
  *                                      (beacon-node/test/spec/general/bls.ts `aggregate_verify`): one aggregated
  *                                      signature over (pubkey, message) pairs with a message per key, many such jobs
@@ -66,7 +72,8 @@ extern "C" {
  * as it was and so keep the number: blsgpu_randomness_words, blsgpu_aggregate_with_randomness, blsgpu_awr_lanes,
  * blsgpu_verify_same_message, blsgpu_same_message_form, blsgpu_same_message_blocks (and the flag
  * BLSGPU_SAME_BLOCK_CHECK of blsgpu_verify_same_message, which was refused before), blsgpu_aggregate_verify,
- * blsgpu_aggregate_verify_form (with blsgpu_aggregate_verify_stats and the BLSGPU_AV_* flags). */
+ * blsgpu_aggregate_verify_form (with blsgpu_aggregate_verify_stats and the BLSGPU_AV_* flags),
+ * blsgpu_verify_same_message_agg, blsgpu_same_message_agg_lanes. */
 #define BLSGPU_ABI_VERSION 8
 
 /* blsgpu_batch.job_flags bits (reference VerifySignatureOpts, chain/bls/interface.ts:3-18) */
@@ -387,6 +394,32 @@ uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags);
  * BLSGPU_SAME_BLOCK_CHECK, else ceil(n_groups / 1024); block b is groups [1024 b, min(n_groups, 1024 (b + 1))).  1024 is
  * the default of option "group_sets", taken as a constant.  Pure host code. */
 uint32_t blsgpu_same_message_blocks(uint32_t n_groups, uint32_t flags);
+
+/* blsgpu_verify_same_message that also returns, per group, the aggregate of the signatures that verified: what the
+ * attestation pool folds into its running aggregate, from the signatures the call decoded once.  Every argument up to
+ * `stats` is as in blsgpu_verify_same_message, and set_result, group_result and every field of stats but device_ms are,
+ * for every input, seed and flags, what that call answers; its error rules hold, for the new outputs too (nothing is
+ * written to any output unless the call returns BLSGPU_OK).
+ * Set k of group g is summed when set_result[k] == 1 and (agg_include is null or agg_include[k] != 0) -- a set the pool
+ * already holds is still verified but masked out of the sum.  agg_count[g] = the sets summed; out_sig[out_sig_len * g] =
+ * Signature.toBytes() of A_g = sum sig_k over them, out_sig_len 96 (compressed) or 192.  A group with agg_count[g] == 0
+ * (empty, every set failed, or masked out entirely) writes all-zero bytes; a sum equal to the identity with agg_count[g]
+ * > 0 is encoded as the identity (0xc0 / 0x40 then zeros), as blsgpu_aggregate_signatures does.  The aggregate does not
+ * depend on seed.  Groups never affect each other.
+ * BLSGPU_ERR_ARGS also for a null out_sig or agg_count with n_groups > 0 and for an out_sig_len other than 96 / 192.
+ * After the retry phase one more segmented sum (a mixed addition per set) and one serialization run on the helper
+ * stream before the results are copied back. */
+int blsgpu_verify_same_message_agg(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
+                                   const uint8_t* msgs /* [32 * n_groups] */, const uint8_t* pk_bytes,
+                                   const uint32_t* pk_index, const uint8_t* sigs, uint32_t sig_stride,
+                                   const uint32_t* sig_len, uint64_t seed, uint32_t flags,
+                                   int8_t* set_result /* [n_sets] */, int8_t* group_result /* [n_groups], nullable */,
+                                   blsgpu_same_message_stats* stats /* nullable */,
+                                   const uint8_t* agg_include /* [n_sets], nullable */,
+                                   uint8_t* out_sig /* [out_sig_len * n_groups] */, uint32_t out_sig_len /* 96 | 192 */,
+                                   uint32_t* agg_count /* [n_groups] */);
+/* Lanes per group that sum takes for a call of this shape: the rule of blsgpu_sig_agg_lanes.  Pure host code. */
+uint32_t blsgpu_same_message_agg_lanes(uint32_t n_groups, uint32_t n_sets);
 
 #define BLSGPU_AV_VALIDATE_KEYS 1u /* keys are untrusted: KeyValidate each (PublicKey.fromBytes(pk, validate = true)) */
 #define BLSGPU_AV_LANE_FORMS 2u    /* diagnostics / tests: take the large-call kernel forms whatever the size */

@@ -13,6 +13,8 @@ reference's own functions (same names in snake_case, same argument meaning and e
 * verify_signature_sets_same_message  IBlsVerifier.verifySignatureSetsSameMessage (chain/bls/interface.ts;
                                  multithread/index.ts + jobItem.ts: aggregate with randomness, verify the one set,
                                  retry every set on its own when that fails)
+* verify_and_aggregate_same_message  the same, and the aggregate of the signatures that verified: what
+                                 attestationPool.add folds into the pool's aggregate (chain/opPools/attestationPool.ts)
 * aggregate_verify               beacon-node/test/spec/general/bls.ts `aggregate_verify` (blst-ts aggregateVerify(msgs,
                                  pks, sig) over untrusted keys, a message per key; any error -> False)
 * verify                         beacon-node/test/spec/general/bls.ts `verify` (one untrusted key; any error -> False)
@@ -285,3 +287,48 @@ def verify_same_message_groups(ctx: Context, groups, messages, seed=0, block_che
                                         sig_stride=stride, seed=seed,
                                         flags=SAME_BLOCK_CHECK if block_check else 0)
     return [[int(r) == 1 for r in res[first[g]: first[g + 1]]] for g in range(len(groups))]
+
+
+def verify_and_aggregate_same_message_groups(ctx: Context, groups, messages, include=None, seed=0, block_check=False):
+    """verify_same_message_groups that also returns each group's aggregate of the signatures that verified, in ONE
+    device call (Context.verify_same_message_agg).  include (optional): per group a list with one truthy / falsy entry
+    per set, or None for all -- a falsy set is verified but left out of the aggregate (one the pool already holds).
+    A list with one (bools, aggregate96 or None, count) per group: the aggregate is Signature.toBytes() of the sum
+    over the `count` sets that verified and were included, None when there is none."""
+    groups = [list(g) for g in groups]
+    messages = [bytes(m)[:32].ljust(32, b"\0") for m in messages]
+    if len(messages) != len(groups):
+        raise ValueError("one message per group")
+    if include is not None and len(include) != len(groups):
+        raise ValueError("one include list (or None) per group")
+    if not groups:
+        return []
+    first = np.cumsum([0] + [len(g) for g in groups])
+    inc = None
+    if include is not None:
+        inc = np.ones(int(first[-1]), np.uint8)
+        for g, m in enumerate(include):
+            if m is None:
+                continue
+            if len(m) != len(groups[g]):
+                raise ValueError(f"group {g}: one include entry per set")
+            inc[first[g]: first[g + 1]] = [1 if x else 0 for x in m]
+    pkb, pki, buf, sig_len, stride = _same_message_arrays([s for g in groups for s in g])
+    if first[-1] == 0:
+        pkb = b""  # no set at all: either key mode
+    res, _, _, out, cnt = ctx.verify_same_message_agg(first, b"".join(messages), buf, pk_bytes=pkb, pk_index=pki,
+                                                      sig_len=sig_len, sig_stride=stride, seed=seed,
+                                                      flags=SAME_BLOCK_CHECK if block_check else 0, include=inc)
+    return [([int(r) == 1 for r in res[first[g]: first[g + 1]]], out[g] if cnt[g] else None, int(cnt[g]))
+            for g in range(len(groups))]
+
+
+def verify_and_aggregate_same_message(ctx: Context, sets, message: bytes, seed=0):
+    """verify_signature_sets_same_message and, from the same device call, the aggregate the attestation pool folds in:
+    (a list with one bool per set, Signature.toBytes() (96 bytes) of the sum of the signatures that verified, or None
+    when none did).  Raises BlstError("Empty signature set") for no sets."""
+    sets = list(sets)
+    if not sets:
+        raise BlstError(10)
+    bools, agg, _ = verify_and_aggregate_same_message_groups(ctx, [sets], [message], seed=seed)[0]
+    return bools, agg

@@ -142,6 +142,20 @@ struct SameBlocks {
   }
 };
 
+// blsgpu_verify_same_message_agg: what the aggregate phase adds, in a buffer of its own (d_msmB, which no phase of the
+// call uses; hl::Same, hl::SameRetry and hl::SameBlocks are as without it), sized with the group phase's buffers.  Byte
+// offsets, every field on a 256-byte boundary:
+//   include (a byte per set, copied up with the inputs) | sums (a Jacobian G2 per group, stride G) | counts (a word per
+//   group) | out (out_len bytes per group)
+struct SameAgg {
+  size_t inc, sums, count, out, total, total_words;
+  SameAgg(size_t G, size_t n, size_t out_len) {
+    Carve c;
+    inc = c.take(n), sums = c.take(G * kG2J * 4), count = c.take(G * 4), out = c.take(G * out_len);
+    total = c.at, total_words = total / 4;
+  }
+};
+
 // blsgpu_aggregate_verify: J jobs over n pairs, U unique messages, C planned Miller chunks (aggverify_plan.hpp).
 // Items: pair k is item k, job j's (-g1, signature) item is item n + j, so the per-item arrays have stride T = n + J;
 // G2 columns: unique message u is column u, job j's signature column U + j, so the per-message arrays have stride

@@ -324,15 +324,25 @@ void same_pairing_phase(const PipelineBuffers& pm, uint32_t n_items, const uint3
   same_miller_half(pm, n_items, iota, pk_aff, include, msg_idx, F, lane, s);
   same_check_half(n_items, S, F, Gs, ok, lane, s);
 }
-}  // namespace
+// The aggregate outputs of blsgpu_verify_same_message_agg; blsgpu_verify_same_message has none.
+struct SameAggOut {
+  const uint8_t* include;  // [n_sets], nullable
+  uint8_t* out_sig;
+  uint32_t out_sig_len;
+  uint32_t* count;
+};
 
-int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first, const uint8_t* msgs,
-                               const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
-                               uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed, uint32_t flags,
-                               int8_t* set_result, int8_t* group_result, blsgpu_same_message_stats* stats) {
+// The body of both same-message verification calls.  agg null: blsgpu_verify_same_message, which launches what it
+// always launched.  Else the aggregate phase follows the retry phase.
+int verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first, const uint8_t* msgs,
+                        const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs, uint32_t sig_stride,
+                        const uint32_t* sig_len, uint64_t seed, uint32_t flags, int8_t* set_result,
+                        int8_t* group_result, blsgpu_same_message_stats* stats, const SameAggOut* agg) {
   if (!ctx || ctx->devs.empty() || !group_first || !msgs || !sigs || !sig_len || !set_result) return BLSGPU_ERR_ARGS;
   if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
   if (sig_stride < 96 || (flags & ~(BLSGPU_SAME_LANE_FORMS | BLSGPU_SAME_BLOCK_CHECK))) return BLSGPU_ERR_ARGS;
+  if (agg && (agg->out_sig_len != 96 && agg->out_sig_len != 192)) return BLSGPU_ERR_ARGS;
+  if (agg && n_groups && (!agg->out_sig || !agg->count)) return BLSGPU_ERR_ARGS;
   if (n_groups == 0) {
     if (stats) memset(stats, 0, sizeof *stats);
     return BLSGPU_OK;
@@ -341,6 +351,8 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
   if (int e = check_group_layout(a)) return e;
   const uint32_t n = a.n, G = n_groups;
   std::vector<int8_t> h_set(n), h_grp(G);
+  std::vector<uint8_t> h_agg(agg ? (size_t)G * agg->out_sig_len : 0);
+  std::vector<uint32_t> h_cnt(agg ? G : 0);
   blsgpu_same_message_stats st;
   memset(&st, 0, sizeof st);
   const int rc = helper_call(ctx, true, [&](Device& d, Slot& sl, hipStream_t s) -> int {
@@ -382,6 +394,9 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
         sl.d_msmW.ensure(lb.work_words);
         sl.d_res.ensure(lb.bytes_total);
       }
+      // the aggregate phase's buffer too: one no other phase of the call uses
+      const hl::SameAgg la(G, n, agg ? agg->out_sig_len : 0);
+      if (agg) sl.d_msmB.ensure(la.total_words);
       streams_used = true;
       uint8_t* din = sl.d_in.p;
       uint8_t* db = sl.d_bytes.p;
@@ -395,6 +410,8 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
       HIPCHK(hipMemcpyAsync(din + l.umsg, umsgs.data(), (size_t)U * 32, hipMemcpyHostToDevice, s));
       HIPCHK(hipMemcpyAsync(din + l.gmsg, gmsg.data(), (size_t)G * 4, hipMemcpyHostToDevice, s));
       HIPCHK(hipMemcpyAsync(din + l.iota, iota.data(), (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
+      uint8_t* da = agg ? reinterpret_cast<uint8_t*>(sl.d_msmB.p) : nullptr;
+      if (agg && agg->include && n) HIPCHK(hipMemcpyAsync(da + la.inc, agg->include, n, hipMemcpyHostToDevice, s));
       AwrBuffers ab_pk = ab;  // the G1 sum runs beside the G2 sum: its own window scratch
       ab_pk.tab = w + l.w_tab_pk;
       uint32_t* g_pk_aff = w + l.w_pk_aff;
@@ -555,6 +572,15 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
         HIPCHK(hipGetLastError());
         if (lane_r) st.form |= 2;
       }
+      // ---- aggregate phase: each group's sum over the sets that answered 1, from the signatures decoded once
+      if (agg) {
+        launch_same_agg(pb.sig_aff, n, d_sres, agg->include ? da + la.inc : nullptr, ab.group_first, G,
+                        reinterpret_cast<uint32_t*>(da + la.sums), reinterpret_cast<uint32_t*>(da + la.count),
+                        da + la.out, agg->out_sig_len, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_agg.data(), da + la.out, h_agg.size(), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_cnt.data(), da + la.count, (size_t)G * 4, hipMemcpyDeviceToHost, s));
+      }
       if (n) HIPCHK(hipMemcpyAsync(h_set.data(), d_sres, n, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       st.device_ms = ms_since(t0);
@@ -573,9 +599,35 @@ int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_
     if (n) memcpy(set_result, h_set.data(), n);
     if (group_result) memcpy(group_result, h_grp.data(), G);
     if (stats) *stats = st;
+    if (agg) {
+      memcpy(agg->out_sig, h_agg.data(), h_agg.size());
+      memcpy(agg->count, h_cnt.data(), (size_t)G * 4);
+    }
   }
   return rc;
 }
+}  // namespace
+
+int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first, const uint8_t* msgs,
+                               const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
+                               uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed, uint32_t flags,
+                               int8_t* set_result, int8_t* group_result, blsgpu_same_message_stats* stats) {
+  return verify_same_message(ctx, n_groups, group_first, msgs, pk_bytes, pk_index, sigs, sig_stride, sig_len, seed,
+                             flags, set_result, group_result, stats, nullptr);
+}
+
+int blsgpu_verify_same_message_agg(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
+                                   const uint8_t* msgs, const uint8_t* pk_bytes, const uint32_t* pk_index,
+                                   const uint8_t* sigs, uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed,
+                                   uint32_t flags, int8_t* set_result, int8_t* group_result,
+                                   blsgpu_same_message_stats* stats, const uint8_t* agg_include, uint8_t* out_sig,
+                                   uint32_t out_sig_len, uint32_t* agg_count) {
+  const SameAggOut agg{agg_include, out_sig, out_sig_len, agg_count};
+  return verify_same_message(ctx, n_groups, group_first, msgs, pk_bytes, pk_index, sigs, sig_stride, sig_len, seed,
+                             flags, set_result, group_result, stats, &agg);
+}
+
+uint32_t blsgpu_same_message_agg_lanes(uint32_t n_groups, uint32_t n_sets) { return sig_agg_lanes(n_groups, n_sets); }
 
 // ---- batched AggregateVerify -----------------------------------------------------------------------------------
 // A job's signature is one more pair of the job, (-g1, sig): k pairs are k + 1 Miller items in the job's own

@@ -225,6 +225,13 @@ void launch_sig_aggregate(const PipelineBuffers& b, const uint32_t* group_first,
 // group; agg_status[g] becomes the group's status (EMPTY_AGGREGATE for an empty group)
 void launch_sig_agg_serialize(const uint32_t* group_first, uint32_t n_groups, const uint32_t* agg, int8_t* agg_status,
                               uint8_t* out, uint32_t out_len, hipStream_t s);
+// blsgpu_verify_same_message_agg (k_sigagg.hip): group g's sum over its sets k with set_result[k] == 1 and (include
+// null or include[k]), from sig_aff (stride n_sets) as launch_sig_decode left it, on the lanes of
+// sig_agg_lanes(n_groups, n_sets); agg (W_G2J SoA, stride n_groups), count[g] = the sets summed, out[out_len * g] = Signature.toBytes() of the
+// sum (zeros when count[g] is 0)
+void launch_same_agg(const uint32_t* sig_aff, uint32_t n_sets, const int8_t* set_result, const uint8_t* include,
+                     const uint32_t* group_first, uint32_t n_groups, uint32_t* agg, uint32_t* count, uint8_t* out,
+                     uint32_t out_len, hipStream_t s);
 // aggregateWithRandomness over groups of sets (k_awr.hip): group g owns sets [group_first[g], group_first[g+1]); per
 // group P = sum r_k pk_k (G1) and S = sum r_k sig_k (G2), r_k the batch scalar of words[k] (never 0).
 struct AwrBuffers {

@@ -62,6 +62,8 @@ EXPORTED_SYMBOLS = [
     "blsgpu_same_message_blocks",
     "blsgpu_aggregate_verify",
     "blsgpu_aggregate_verify_form",
+    "blsgpu_verify_same_message_agg",
+    "blsgpu_same_message_agg_lanes",
 ]
 SAME_LANE_FORMS = 1
 SAME_BLOCK_CHECK = 4  # BLSGPU_SAME_BLOCK_CHECK: one check per block of 1024 groups, then the descent
@@ -212,6 +214,11 @@ def load():
     lib.blsgpu_same_message_form.restype = u32
     lib.blsgpu_same_message_blocks.argtypes = [u32, u32]
     lib.blsgpu_same_message_blocks.restype = u32
+    lib.blsgpu_verify_same_message_agg.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, vp, ctypes.c_uint64, u32, vp, vp,
+                                                   vp, vp, vp, u32, vp]
+    lib.blsgpu_verify_same_message_agg.restype = ctypes.c_int
+    lib.blsgpu_same_message_agg_lanes.argtypes = [u32, u32]
+    lib.blsgpu_same_message_agg_lanes.restype = u32
     lib.blsgpu_aggregate_verify.argtypes = [vp, u32, vp, vp, vp, u32, vp, vp, u32, vp, u32, vp, vp, vp]
     lib.blsgpu_aggregate_verify.restype = ctypes.c_int
     lib.blsgpu_aggregate_verify_form.argtypes = [u32, u32]
@@ -295,6 +302,12 @@ def same_message_form(n_items, flags=0):
     """The kernel forms blsgpu_verify_same_message gives a phase of n_items pairings (C-ABI blsgpu_same_message_form,
     pure host code): 0 = cooperative, 1 = lane forms."""
     return int(load().blsgpu_same_message_form(n_items, flags))
+
+
+def same_message_agg_lanes(n_groups, n_sets):
+    """Lanes per group the aggregate phase of blsgpu_verify_same_message_agg gives a call of this shape (C-ABI
+    blsgpu_same_message_agg_lanes, pure host code): the rule of sig_agg_lanes."""
+    return int(load().blsgpu_same_message_agg_lanes(n_groups, n_sets))
 
 
 def same_message_blocks(n_groups, flags=0):
@@ -634,6 +647,54 @@ class Context:
         if rc != OK:
             raise RuntimeError(f"blsgpu_verify_same_message -> {code_name(rc)}")
         return res[:n], gres[:n_groups], st
+
+    def verify_same_message_agg(self, group_first, msgs, sigs, pk_bytes=None, pk_index=None, sig_len=None,
+                                sig_stride=None, seed=0, flags=0, include=None, out_sig_len=96):
+        """verify_same_message that also returns each group's aggregate of the signatures that verified
+        (blsgpu_verify_same_message_agg).  include (a byte per set, default all): a set with include 0 is verified
+        but left out of the sum.  Returns (set_result, group_result, SameMessageStats -- all as verify_same_message
+        answers --, out_sig: list of out_sig_len-byte encodings, zero bytes for a group that summed nothing,
+        agg_count uint32 array: the sets summed per group).  ValueError for a malformed layout, before the library is
+        called; RuntimeError for a call-level failure."""
+        gf, buf, sl, stride, pkb, pki = awr_layout(group_first, sigs, pk_bytes, pk_index, sig_len, sig_stride)
+        n_groups = len(gf) - 1
+        n = int(gf[-1])
+        if out_sig_len not in (96, 192):
+            raise ValueError("out_sig_len must be 96 or 192")
+        m = _u8(msgs)
+        if len(m) != 32 * n_groups:
+            raise ValueError(f"{n_groups} groups need {32 * n_groups} message bytes, got {len(m)}")
+        inc = None
+        if include is not None:
+            inc = np.ascontiguousarray(include, dtype=np.uint8)
+            if inc.shape != (n,):
+                raise ValueError(f"{n} sets need {n} include bytes, got shape {inc.shape}")
+            if n == 0:
+                inc = None
+        if len(m) == 0:
+            m = np.zeros(1, np.uint8)
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        if len(sl) == 0:
+            sl = np.zeros(1, np.uint32)
+        if pkb is not None and len(pkb) == 0:
+            pkb = np.zeros(1, np.uint8)
+        if pki is not None and len(pki) == 0:
+            pki = np.zeros(1, np.uint32)
+        res = np.zeros(max(n, 1), np.int8)
+        gres = np.zeros(max(n_groups, 1), np.int8)
+        out = np.zeros(max(n_groups, 1) * out_sig_len, np.uint8)
+        cnt = np.zeros(max(n_groups, 1), np.uint32)
+        st = SameMessageStats()
+        rc = self._lib.blsgpu_verify_same_message_agg(
+            self.h, n_groups, gf.ctypes.data, m.ctypes.data, None if pkb is None else pkb.ctypes.data,
+            None if pki is None else pki.ctypes.data, buf.ctypes.data, stride, sl.ctypes.data, seed, flags,
+            res.ctypes.data, gres.ctypes.data, ctypes.byref(st), None if inc is None else inc.ctypes.data,
+            out.ctypes.data, out_sig_len, cnt.ctypes.data)
+        if rc != OK:
+            raise RuntimeError(f"blsgpu_verify_same_message_agg -> {code_name(rc)}")
+        return (res[:n], gres[:n_groups], st,
+                [out[out_sig_len * g: out_sig_len * (g + 1)].tobytes() for g in range(n_groups)], cnt[:n_groups])
 
     def aggregate_verify(self, job_first, msgs, sigs, pk_bytes=None, pk_len=96, pk_index=None, sig_len=None,
                          sig_stride=None, flags=0):

@@ -106,6 +106,7 @@ class BlsGpuVerifier {
     this.seed = opts.seed || 0; // 0 = OS CSPRNG batch scalars; fixed only for comparison runs
     this.fusedSameMessage = !!opts.fusedSameMessage;
     this.sameMessageBlockCheck = this.fusedSameMessage && !!opts.sameMessageBlockCheck;
+    this.blockCheckOption = !!opts.sameMessageBlockCheck; // verifyAndAggregateSameMessage is always one device call
     // verifyOnMainThread calls are latency-critical exceptions to the pool (the block proposer signature): they run on
     // the device's urgent lane.  The single-thread verifier sends every call that way and keeps the shared pipeline.
     this.urgentMainThread = true;
@@ -254,7 +255,29 @@ class BlsGpuVerifier {
    * @param {{batchable?: boolean}} opts
    * @returns {Promise<boolean[]>}
    */
-  async verifySignatureSetsSameMessage(sets, message, opts = {}) {
+  verifySignatureSetsSameMessage(sets, message, opts = {}) {
+    return this.queueSameMessage(sets, message, opts, false);
+  }
+
+  /**
+   * verifySignatureSetsSameMessage and, from the same device call, what the attestation pool does with the sets that
+   * passed (attestationPool.add: Signature.aggregate of the pool's aggregate and each new signature): resolves to
+   * {results: one boolean per set, signature: the 96-byte aggregate of the signatures that verified and whose set does
+   * not say `aggregate: false` (a set the pool already holds is verified but not added again) or null when there is
+   * none, count: how many were summed}.  Always one addon.verifySameMessageAggregate call per pubkey mode over the
+   * calls waiting in one flush, whatever fusedSameMessage says; sameMessageBlockCheck is honoured.  Rejects as
+   * verifySignatureSetsSameMessage does.
+   * @param {Array<{publicKey: any, signature: Uint8Array, aggregate?: boolean}>} sets
+   * @param {Uint8Array} message
+   * @param {{batchable?: boolean}} opts
+   * @returns {Promise<{results: boolean[], signature: Buffer | null, count: number}>}
+   */
+  verifyAndAggregateSameMessage(sets, message, opts = {}) {
+    return this.queueSameMessage(sets, message, opts, true);
+  }
+
+  /** Both same-message methods (async: a throw here is a rejection; the wrappers add no promise of their own). */
+  async queueSameMessage(sets, message, opts, aggregate) {
     if (this.closed) throw new QueueError({code: QUEUE_ABORTED});
     if (sets.length === 0) throw new Error(opts.verifyOnMainThread ? "Empty signature set" : "Empty results array");
     const refs = sets.map((s) => this.pkRef(s.publicKey));
@@ -263,7 +286,7 @@ class BlsGpuVerifier {
       for (const r of refs)
         if (r.bytes === undefined || r.bytes.length !== 96)
           throw new TypeError("BlsGpuVerifier: pubkeys of a bytes-mode job must serialize to 96 uncompressed bytes");
-    const call = {sets, refs, table, message, batchable: !!opts.batchable};
+    const call = {sets, refs, table, message, batchable: !!opts.batchable, aggregate};
     this.samePending++;
     const p = new Promise((resolve, reject) => {
       call.resolve = resolve;
@@ -371,12 +394,15 @@ class BlsGpuVerifier {
     this.sameTimer = null;
     const calls = this.sameQueued.splice(0, this.sameQueued.length);
     for (const mode of [true, false]) {
-      const part = calls.filter((c) => c.table === mode);
+      const part = calls.filter((c) => c.table === mode && !c.aggregate);
       if (part.length) this.aggregateSameMessage(part, mode);
+      const agg = calls.filter((c) => c.table === mode && c.aggregate);
+      if (agg.length) this.verifyAndAggregateFlush(agg, mode);
     }
   }
 
-  aggregateSameMessage(calls, tableMode) {
+  /** The arrays of one device call over `calls`, one group per call. */
+  packSameMessage(calls, tableMode) {
     let n = 0;
     for (const c of calls) n += c.sets.length;
     const groupFirst = new Uint32Array(calls.length + 1);
@@ -396,6 +422,11 @@ class BlsGpuVerifier {
       });
     });
     groupFirst[calls.length] = k;
+    return {groupFirst, pkBytes, pkIndex, sigs, sigLen};
+  }
+
+  aggregateSameMessage(calls, tableMode) {
+    const {groupFirst, pkBytes, pkIndex, sigs, sigLen} = this.packSameMessage(calls, tableMode);
     this.stats.sameMessageAggregations++;
     if (this.fusedSameMessage) return this.verifySameMessageFused(calls, groupFirst, pkBytes, pkIndex, sigs, sigLen);
     addon.aggregateWithRandomness(this.ctx, groupFirst, pkBytes, pkIndex, sigs, sigLen, SIG_STRIDE, this.seed, 96, SIG_STRIDE).then(
@@ -441,6 +472,48 @@ class BlsGpuVerifier {
         for (const c of calls) c.reject(err.code === QUEUE_ABORTED ? new QueueError({code: QUEUE_ABORTED}) : err);
       }
     );
+  }
+
+  /**
+   * verifyAndAggregateSameMessage: the waiting calls of one pubkey mode in one addon.verifySameMessageAggregate call.
+   * Call i resolves to its sets' booleans and the aggregate of its group; stats and metrics as verifySameMessageFused.
+   */
+  verifyAndAggregateFlush(calls, tableMode) {
+    const {groupFirst, pkBytes, pkIndex, sigs, sigLen} = this.packSameMessage(calls, tableMode);
+    const msgs = new Uint8Array(32 * calls.length);
+    calls.forEach((c, ci) => msgs.set(c.message.subarray(0, 32), 32 * ci));
+    let include = null;
+    if (calls.some((c) => c.sets.some((s) => s.aggregate === false))) {
+      include = new Uint8Array(groupFirst[calls.length]).fill(1);
+      calls.forEach((c, ci) => c.sets.forEach((s, i) => (include[groupFirst[ci] + i] = s.aggregate === false ? 0 : 1)));
+    }
+    const flags = this.blockCheckOption ? SAME_BLOCK_CHECK : 0;
+    this.stats.sameMessageAggregations++;
+    addon
+      .verifySameMessageAggregate(this.ctx, groupFirst, msgs, pkBytes, pkIndex, sigs, sigLen, SIG_STRIDE, this.seed, flags, include, 96)
+      .then(
+        (r) => {
+          const m = this.metrics && this.metrics.blsThreadPool;
+          calls.forEach((c, ci) => {
+            if (r.groupResult[ci] !== 1) {
+              this.stats.sameMessageRetries++;
+              this.stats.sameMessageRetrySets += c.sets.length;
+              if (m && m.sameMessageRetryJobs) m.sameMessageRetryJobs.inc(1);
+              if (m && m.sameMessageRetrySets) m.sameMessageRetrySets.inc(c.sets.length);
+            }
+            const count = r.aggCount[ci];
+            c.resolve({
+              results: Array.from(r.setResult.subarray(groupFirst[ci], groupFirst[ci + 1]), (x) => x === 1),
+              signature: count ? Buffer.from(r.outSig.slice(96 * ci, 96 * ci + 96)) : null,
+              count,
+            });
+          });
+        },
+        (err) => {
+          // call-level failure (device error, entropy, closed context): reject every call, never resolve false
+          for (const c of calls) c.reject(err.code === QUEUE_ABORTED ? new QueueError({code: QUEUE_ABORTED}) : err);
+        }
+      );
   }
 
   /** (P, message, S) as its own ordinary job; anything but `true` retries the call's sets one by one. */

@@ -39,6 +39,11 @@
  *                   uniqueMessages, form, deviceMs}}>
  *     blsgpu_verify_same_message as napi_create_async_work, the same lifetime rules as aggregateWithRandomness.
  *     flags: BLSGPU_SAME_LANE_FORMS (1) and BLSGPU_SAME_BLOCK_CHECK (4); any other bit is a RangeError here.
+ *   verifySameMessageAggregate(ctx, groupFirst, msgs, pkBytes, pkIndex, sigs, sigLen, sigStride, seed, flags,
+ *                              include: Uint8Array | null (a byte per set; 0 = verified but not summed), outSigLen 96|192)
+ *       -> Promise<{setResult, groupResult, stats (as verifySameMessage), outSig: Uint8Array (outSigLen bytes per group,
+ *                   zeros for a group that summed nothing), aggCount: Uint32Array}>
+ *     blsgpu_verify_same_message_agg as napi_create_async_work, the same lifetime rules as verifySameMessage.
  *   aggregateVerify(ctx, jobFirst: Uint32Array, msgs: Uint8Array (32 bytes per pair), pkBytes: Uint8Array | null, pkLen,
  *                   pkIndex: Uint32Array | null, sigs: Uint8Array (one per job), sigLen: Uint32Array, sigStride, flags)
  *       -> Promise<{jobResult: Int8Array, firstBad: Uint32Array, stats: {pairs, uniqueMessages, millerItems,
@@ -759,6 +764,12 @@ typedef struct {
   uint8_t* sigs;
   int8_t* set_result;
   int8_t* group_result;
+  /* verifySameMessageAggregate only (agg): the mask (nullable), the groups' aggregates and their counts */
+  int agg;
+  uint32_t out_sig_len;
+  uint8_t* include;
+  uint8_t* out_sig;
+  uint32_t* agg_count;
   blsgpu_same_message_stats stats;
   int rc;
   napi_deferred deferred;
@@ -774,6 +785,9 @@ static void same_free(SameCall* a) {
   free(a->sigs);
   free(a->set_result);
   free(a->group_result);
+  free(a->include);
+  free(a->out_sig);
+  free(a->agg_count);
   free(a);
 }
 
@@ -781,6 +795,13 @@ static void same_free(SameCall* a) {
 static void same_execute(napi_env env, void* data) {
   (void)env;
   SameCall* a = (SameCall*)data;
+  if (a->agg) {
+    a->rc = blsgpu_verify_same_message_agg(a->box->ctx, a->n_groups, a->group_first, a->msgs, a->pk_bytes, a->pk_index,
+                                           a->sigs, a->stride, a->sig_len, a->seed, a->flags, a->set_result,
+                                           a->group_result, &a->stats, a->include, a->out_sig, a->out_sig_len,
+                                           a->agg_count);
+    return;
+  }
   a->rc = blsgpu_verify_same_message(a->box->ctx, a->n_groups, a->group_first, a->msgs, a->pk_bytes, a->pk_index,
                                      a->sigs, a->stride, a->sig_len, a->seed, a->flags, a->set_result, a->group_result,
                                      &a->stats);
@@ -817,19 +838,28 @@ static void same_complete(napi_env env, napi_status st, void* data) {
     napi_create_double(env, a->stats.device_ms, &ms);
     napi_set_named_property(env, stats, "deviceMs", ms);
     napi_set_named_property(env, out, "stats", stats);
+    if (a->agg) {
+      napi_set_named_property(env, out, "outSig",
+                              copy_out(env, napi_uint8_array, a->out_sig, (size_t)a->n_groups * a->out_sig_len, 1));
+      napi_set_named_property(env, out, "aggCount", copy_out(env, napi_uint32_array, a->agg_count, a->n_groups, 4));
+    }
     napi_resolve_deferred(env, a->deferred, out);
   }
   napi_delete_async_work(env, a->work);
   same_free(a);
 }
 
-static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
-  size_t argc = 10;
-  napi_value argv[10];
+/* verifySameMessage (agg 0: ten arguments) and verifySameMessageAggregate (agg 1: include and outSigLen after them) */
+static napi_value verify_same_message_call(napi_env env, napi_callback_info info, int agg) {
+  size_t argc = 12;
+  napi_value argv[12];
   CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 10) {
+  if (argc < (agg ? 12u : 10u)) {
     napi_throw_type_error(env, NULL,
-                          "verifySameMessage(ctx, groupFirst, msgs, pkBytes, pkIndex, sigs, sigLen, sigStride, seed, flags)");
+                          agg ? "verifySameMessageAggregate(ctx, groupFirst, msgs, pkBytes, pkIndex, sigs, sigLen, "
+                                "sigStride, seed, flags, include, outSigLen)"
+                              : "verifySameMessage(ctx, groupFirst, msgs, pkBytes, pkIndex, sigs, sigLen, sigStride, "
+                                "seed, flags)");
     return NULL;
   }
   CtxBox* box = get_open_box(env, argv[0]);
@@ -846,6 +876,16 @@ static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
                           "verifySameMessage: groupFirst, pkIndex, sigLen Uint32Array; msgs, pkBytes, sigs Uint8Array");
     return NULL;
   }
+  size_t n_inc = 0;
+  void* inc = NULL;
+  uint32_t out_sig_len = 0;
+  if (agg) {
+    if (opt_typed(env, argv[10], napi_uint8_array, &inc, &n_inc)) {
+      napi_throw_type_error(env, NULL, "verifySameMessageAggregate: include is a Uint8Array or null");
+      return NULL;
+    }
+    napi_get_value_uint32(env, argv[11], &out_sig_len);
+  }
   uint32_t stride = 0, flags = 0;
   double seed = 0;
   napi_get_value_uint32(env, argv[7], &stride);
@@ -859,6 +899,7 @@ static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
   ok = ok && gfw[n_gf - 1] == n_len && n_len <= (1u << 20) && n_bytes >= (size_t)stride * n_len;
   ok = ok && (pkb ? n_pkb == 96 * n_len : n_pki == n_len);
   for (size_t k = 0; ok && stride < 192 && k < n_len; k++) ok = ((const uint32_t*)slen)[k] != 192;
+  if (agg) ok = ok && (out_sig_len == 96 || out_sig_len == 192) && (!inc || n_inc == n_len);
   if (!ok) {
     napi_throw_range_error(env, "BLSGPU_ERR_ARGS", "verifySameMessage: inconsistent array sizes");
     return NULL;
@@ -882,9 +923,18 @@ static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
   a->sigs = (uint8_t*)dup_bytes(sigs, (size_t)stride * n_len);
   a->set_result = (int8_t*)calloc((size_t)n_len + 1, 1);
   a->group_result = (int8_t*)calloc((size_t)a->n_groups + 1, 1);
+  a->agg = agg;
+  int agg_ok = 1;
+  if (agg) {
+    a->out_sig_len = out_sig_len;
+    if (inc) a->include = (uint8_t*)dup_bytes(inc, n_inc);
+    a->out_sig = (uint8_t*)calloc((size_t)a->n_groups * out_sig_len + 1, 1);
+    a->agg_count = (uint32_t*)calloc((size_t)a->n_groups + 1, 4);
+    agg_ok = (!inc || a->include) && a->out_sig && a->agg_count;
+  }
   napi_value promise, name;
   if (!a->group_first || !a->msgs || (!a->pk_bytes && !a->pk_index) || !a->sig_len || !a->sigs || !a->set_result ||
-      !a->group_result || napi_create_promise(env, &a->deferred, &promise) != napi_ok ||
+      !a->group_result || !agg_ok || napi_create_promise(env, &a->deferred, &promise) != napi_ok ||
       napi_create_string_utf8(env, "blsgpu_verify_same_message", NAPI_AUTO_LENGTH, &name) != napi_ok ||
       napi_create_async_work(env, NULL, name, same_execute, same_complete, a, &a->work) != napi_ok) {
     same_free(a);
@@ -900,6 +950,13 @@ static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
     return NULL;
   }
   return promise;
+}
+
+static napi_value VerifySameMessage(napi_env env, napi_callback_info info) {
+  return verify_same_message_call(env, info, 0);
+}
+static napi_value VerifySameMessageAggregate(napi_env env, napi_callback_info info) {
+  return verify_same_message_call(env, info, 1);
 }
 
 /* aggregateVerify: one blsgpu_aggregate_verify call as async work (lifetimes as verifySameMessage: every input is
@@ -1091,6 +1148,7 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
       {"aggregateSignatures", NULL, AggregateSignatures, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"aggregateWithRandomness", NULL, AggregateWithRandomness, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"verifySameMessage", NULL, VerifySameMessage, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
+      {"verifySameMessageAggregate", NULL, VerifySameMessageAggregate, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"aggregateVerify", NULL, AggregateVerify, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);

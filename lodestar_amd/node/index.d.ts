@@ -25,10 +25,14 @@ export type BlsGpuVerifierOpts = {
   fusedSameMessage?: boolean;
   /** true, together with fusedSameMessage: that call passes SAME_BLOCK_CHECK -- the aggregates are checked 1024 at a
    * time under one final exponentiation, and only the groups of a block that fails one by one; the same answers
-   * (default false; ignored without fusedSameMessage) */
+   * (default false; ignored without fusedSameMessage, except by verifyAndAggregateSameMessage, which is always one
+   * device call) */
   sameMessageBlockCheck?: boolean;
 };
 
+/** What addon.verifySameMessageAggregate resolves to (blsgpu_verify_same_message_agg): SameMessageResult and
+ * outSig (outSigLen bytes per group, zeros for a group that summed nothing), aggCount (the sets summed per group). */
+export type SameMessageAggregateResult = SameMessageResult & {outSig: Uint8Array; aggCount: Uint32Array};
 /** What addon.verifySameMessage resolves to (blsgpu_verify_same_message). */
 export type SameMessageResult = {
   /** per set: 1 valid, 0 invalid, -code rejected */
@@ -95,6 +99,17 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
     message: Uint8Array,
     opts?: Omit<VerifySignatureOpts, "verifyOnMainThread">
   ): Promise<boolean[]>;
+  /** verifySignatureSetsSameMessage and, from the same device call (addon.verifySameMessageAggregate,
+   * blsgpu_verify_same_message_agg), the aggregate the attestation pool folds in: `signature` is Signature.toBytes()
+   * (96 bytes) of the sum of the signatures that verified and whose set does not say `aggregate: false` (a set the pool
+   * already holds: verified, not added again), null when there is none; `count` is how many were summed.  The calls
+   * waiting in one flush share one device call per pubkey mode whatever fusedSameMessage says; sameMessageBlockCheck is
+   * honoured.  Rejects as verifySignatureSetsSameMessage does. */
+  verifyAndAggregateSameMessage(
+    sets: {publicKey: GpuPubkey; signature: Uint8Array; aggregate?: boolean}[],
+    message: Uint8Array,
+    opts?: Omit<VerifySignatureOpts, "verifyOnMainThread">
+  ): Promise<{results: boolean[]; signature: Buffer | null; count: number}>;
   /** IBlsVerifier.canAcceptWork: true while fewer than MAX_JOBS_CAN_ACCEPT_WORK (512) jobs are pending. */
   canAcceptWork(): boolean;
   readonly stats: {

@@ -22,6 +22,14 @@ clock
 around the calls, which end in a stream synchronise; medians, minima and maxima are reported.
 
     python tools/bench_same_message.py [--calls 30] [--warmup 5] [--out FILE] [--no-serial]
+
+--aggregate times blsgpu_verify_same_message_agg instead, on 128x128, 16384x1 and 128x128 bad 1%, each
+with and without SAME_BLOCK_CHECK, three legs timed alternately in this process:
+    two_call   verify_same_message, then aggregate_signatures (validate off) of the sets that verified, grouped as
+               they were: the way to the groups' aggregates without the new call, both functions unchanged code
+    one_call   verify_same_message_agg
+    verify     verify_same_message alone: one_call minus this is the cost of the aggregate phase
+The aggregates and counts of the two ways are compared byte for byte before anything is timed.
 """
 import argparse
 import hashlib
@@ -139,6 +147,81 @@ def time_shape(ctx, n_groups, size, bad_groups, calls, warmup, fused_only):
     return out
 
 
+AGG_SHAPES = [SHAPES[0], SHAPES[1], SHAPES[2]]
+
+
+def time_aggregate_shape(ctx, n_groups, size, bad_groups, flags, calls, warmup):
+    pks, gmsgs, sigs = workload(ctx, size, bad_groups)
+    first = np.arange(n_groups + 1, dtype=np.uint32) * size
+    buf = np.frombuffer(sigs, np.uint8)
+    pkb = np.frombuffer(pks, np.uint8)
+    sl = np.full(N_SETS, 96, np.uint32)
+    last = {}
+
+    def verify():
+        last["verify"] = ctx.verify_same_message(first, gmsgs, buf, pk_bytes=pkb, sig_len=sl, sig_stride=96, seed=0,
+                                                 flags=flags)
+
+    def two_call():
+        res, _, _ = ctx.verify_same_message(first, gmsgs, buf, pk_bytes=pkb, sig_len=sl, sig_stride=96, seed=0,
+                                            flags=flags)
+        ok = res == 1
+        if ok.all():
+            out, st, _ = ctx.aggregate_signatures(buf, first, sig_len=sl, sig_stride=96, validate=False)
+            cnt = np.diff(first)
+        else:
+            cnt = np.add.reduceat(ok.astype(np.int64), first[:-1].astype(np.int64))
+            kept = np.concatenate([[0], np.cumsum(cnt)])
+            out, st, _ = ctx.aggregate_signatures(buf.reshape(-1, 96)[ok].reshape(-1), kept, sig_len=sl[ok],
+                                                  sig_stride=96, validate=False)
+        last["two"] = (res, out, cnt)
+
+    def one_call():
+        last["one"] = ctx.verify_same_message_agg(first, gmsgs, buf, pk_bytes=pkb, sig_len=sl, sig_stride=96, seed=0,
+                                                  flags=flags)
+
+    two_call()
+    one_call()
+    res, gres, st, out, cnt = last["one"]
+    want = np.ones(N_SETS, np.int8)
+    want[[g * size for g in range(bad_groups)]] = 0
+    assert (res == want).all() and (last["two"][0] == want).all()
+    assert out == last["two"][1] and (cnt == last["two"][2]).all() and int(cnt.sum()) == N_SETS - bad_groups
+    r = {"groups": n_groups, "group_size": size, "bad_groups": bad_groups, "flags": flags, "form": st.form,
+         "agg_lanes": native_agg_lanes(n_groups)}
+    r.update(timed({"two_call": two_call, "one_call": one_call, "verify": verify}, calls, warmup))
+    r["one_call"]["device_ms_last"] = last["one"][2].device_ms
+    r["one_call_over_two_call"] = r["one_call"]["median_ms"] / r["two_call"]["median_ms"]
+    r["phase_ms"] = r["one_call"]["median_ms"] - r["verify"]["median_ms"]
+    return r
+
+
+def native_agg_lanes(n_groups):
+    from lodestar_amd import native
+
+    return native.same_message_agg_lanes(n_groups, N_SETS)
+
+
+def main_aggregate(a):
+    from lodestar_amd import native
+
+    ctx = native.Context([0])
+    try:
+        shapes = {}
+        for name, g, size, bad in AGG_SHAPES:
+            for flags in (0, SAME_BLOCK_CHECK):
+                shapes[name + ("_blocks" if flags else "")] = time_aggregate_shape(ctx, g, size, bad, flags, a.calls,
+                                                                                   a.warmup)
+    finally:
+        ctx.close()
+    line = json.dumps({"bench": "verify_same_message_agg", "sets": N_SETS, "shapes": shapes})
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=30)
@@ -146,9 +229,12 @@ def main():
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--fused-only", action="store_true", help="time the fused call alone (the serial child)")
     ap.add_argument("--no-serial", action="store_true", help="leave the serial child out")
+    ap.add_argument("--aggregate", action="store_true", help="time verify_same_message_agg against the two-call method")
     a = ap.parse_args()
     if a.calls < 20:
         ap.error("--calls must be at least 20")
+    if a.aggregate:
+        return main_aggregate(a)
     from lodestar_amd import native
 
     ctx = native.Context([0])  # fails loudly without a GPU: there is nothing to time elsewhere
