@@ -11,6 +11,10 @@
  *                                      chain/bls/utils.ts:5-16); table mode aggregates on the GPU instead
  *   blsgpu_pubkeys_upload           <- the pubkey cache the sets draw from (state-transition
  *                                      src/cache/pubkeyCache.ts:56-77, epochContext.ts:702-705)
+ *   blsgpu_pubkeys_upload_compressed <- the same cache filled from what the state holds, state.validators[i].pubkey
+ *                                      (48 bytes compressed; pubkeyCache.ts:56-77, epochContext.ts:702-705): the
+ *                                      decompression PublicKey.fromBytes does there, one square root per key
+ *   blsgpu_pubkeys_read             <- index2pubkey[i] / PublicKey.toBytes() of a cached key
  *   blsgpu_destroy                  <- IBlsVerifier.close (chain/bls/interface.ts:45)
  *   blsgpu_aggregate_pubkeys        <- PublicKey.aggregate(pks).toBytes() (chain/bls/utils.ts:5-16,
  *                                      multithread/index.ts:160)
@@ -73,7 +77,8 @@ extern "C" {
  * blsgpu_verify_same_message, blsgpu_same_message_form, blsgpu_same_message_blocks (and the flag
  * BLSGPU_SAME_BLOCK_CHECK of blsgpu_verify_same_message, which was refused before), blsgpu_aggregate_verify,
  * blsgpu_aggregate_verify_form (with blsgpu_aggregate_verify_stats and the BLSGPU_AV_* flags),
- * blsgpu_verify_same_message_agg, blsgpu_same_message_agg_lanes. */
+ * blsgpu_verify_same_message_agg, blsgpu_same_message_agg_lanes, blsgpu_pubkeys_upload_compressed (with
+ * BLSGPU_PK_VALIDATE), blsgpu_pubkeys_read. */
 #define BLSGPU_ABI_VERSION 8
 
 /* blsgpu_batch.job_flags bits (reference VerifySignatureOpts, chain/bls/interface.ts:3-18) */
@@ -185,6 +190,32 @@ int blsgpu_device_count(const blsgpu_ctx* ctx);
  * with BLSGPU_ERR_ARGS on a device not yet updated, never verify against stale keys. */
 int blsgpu_pubkeys_upload(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* pk96, uint32_t n);
 uint32_t blsgpu_pubkeys_count(const blsgpu_ctx* ctx);
+
+#define BLSGPU_PK_VALIDATE 1u /* keys are untrusted: KeyValidate each (adds the subgroup check) */
+
+/* The same table from 48-byte ZCash compressed encodings, the form state.validators[i].pubkey has (pubkeyCache.ts:56-77,
+ * epochContext.ts:702-705): entries [first_index, first_index + n) from pk48[48 k], decompressed on the devices.
+ * Per-key code, checked in this order: BAD_ENCODING (compression bit clear; infinity bit with any other bit or byte
+ * set; x >= p), POINT_NOT_ON_CURVE (x^3 + 4 is not a square), PK_IS_INFINITY (0xc0 then zeros) and, only with
+ * BLSGPU_PK_VALIDATE, POINT_NOT_IN_GROUP.  Without the flag the keys are trusted, as in the 96-byte upload: an on-curve
+ * point outside G1 is stored.  status (nullable, [n]) receives every key's code (0 = accepted), *first_bad (nullable)
+ * the lowest rejected index within the call or 0xffffffff.  Returns BLSGPU_OK when every key was accepted (the rows
+ * are then stored on every device), otherwise the code of the lowest-index rejected key, with nothing written to any
+ * device's table and blsgpu_pubkeys_count unchanged; status and first_bad are filled in both cases.
+ * BLSGPU_ERR_ARGS, before anything reaches a device and with status and first_bad untouched: a null ctx, an unknown
+ * flag, a null pk48 with n > 0, first_index beyond the table (no gaps), first_index + n not fitting 32 bits.  n == 0
+ * returns BLSGPU_OK (after the ctx and flag checks).  Locking, replicas and the concurrent per-device uploads are those
+ * of blsgpu_pubkeys_upload, as are BLSGPU_ERR_CLOSED and BLSGPU_DEVICE_ERROR. */
+int blsgpu_pubkeys_upload_compressed(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* pk48, uint32_t n,
+                                     uint32_t flags, int8_t* status /* [n], nullable */,
+                                     uint32_t* first_bad /* nullable */);
+
+/* Table readback: out[out_len k] = entry first_index + k of device 0's replica, out_len 96 (big-endian affine x || y,
+ * what PublicKey.fromBytes takes without a square root) or 48 (compressed).  BLSGPU_ERR_ARGS: a null ctx, an out_len
+ * other than 48 / 96, a null out with n > 0, a range reaching past blsgpu_pubkeys_count.  n == 0 returns BLSGPU_OK
+ * (after the ctx and out_len checks).  Synchronous, on device 0 like the other helper calls. */
+int blsgpu_pubkeys_read(blsgpu_ctx* ctx, uint32_t first_index, uint32_t n, uint8_t* out,
+                        uint32_t out_len /* 48 | 96 */);
 
 /* Synchronous verification.  job_result[n_jobs]: 1 valid / 0 invalid / -code.  Returns a call-level
  * status (BLSGPU_OK even when some jobs are invalid or rejected; a HIP failure rejects the jobs of the

@@ -18,6 +18,9 @@ reference's own functions (same names in snake_case, same argument meaning and e
 * aggregate_verify               beacon-node/test/spec/general/bls.ts `aggregate_verify` (blst-ts aggregateVerify(msgs,
                                  pks, sig) over untrusted keys, a message per key; any error -> False)
 * verify                         beacon-node/test/spec/general/bls.ts `verify` (one untrusted key; any error -> False)
+* upload_pubkeys_compressed      state-transition/src/cache/pubkeyCache.ts:56-77 (syncPubkeys: PublicKey.fromBytes of
+                                 every state.validators[i].pubkey; here the GPU decompresses into its table)
+* read_pubkeys                   index2pubkey[i].toBytes() of the keys the table holds
 * process_deposit_signature      state-transition/src/block/processDeposit.ts:54-64 (KeyValidate + verify;
                                  any error -> False: the deposit is skipped, not rejected)
 
@@ -68,6 +71,28 @@ def key_validate(ctx: Context, pubkeys48):
         raise ValueError("48-byte compressed pubkeys expected")
     pk96, st = ctx.key_validate(b"".join(bytes(p) for p in pubkeys48), 48)
     return [pk96[96 * i: 96 * i + 96] if st[i] == 0 else None for i in range(len(pubkeys48))], st
+
+
+def upload_pubkeys_compressed(ctx: Context, first_index: int, pubkeys48, validate=False):
+    """Table entries [first_index, first_index + len(pubkeys48)) from 48-byte compressed keys (trusted, as the keys of
+    the state are; validate: KeyValidate each).  Raises BlstError(code) of the first rejected key -- its index is the
+    error's .index -- and stores nothing then."""
+    pubkeys48 = [bytes(p) for p in pubkeys48]
+    if any(len(p) != 48 for p in pubkeys48):
+        raise ValueError("48-byte compressed pubkeys expected")
+    st, first_bad = ctx.upload_pubkeys_compressed(first_index, b"".join(pubkeys48), validate=validate)
+    if first_bad != 0xFFFFFFFF:
+        err = BlstError(int(st[first_bad]))
+        err.index = first_index + first_bad
+        raise err
+
+
+def read_pubkeys(ctx: Context, first_index: int, n: int, compressed=False):
+    """The table's entries [first_index, first_index + n): a list of 96-byte uncompressed (or 48-byte compressed)
+    encodings."""
+    k = 48 if compressed else 96
+    out = ctx.read_pubkeys(first_index, n, k)
+    return [out[k * i: k * i + k] for i in range(n)]
 
 
 def fast_aggregate_verify(ctx: Context, pubkeys48, message: bytes, signature: bytes) -> bool:

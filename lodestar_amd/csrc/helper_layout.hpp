@@ -199,6 +199,15 @@ struct KeyValidate {
   }
 };
 
+// blsgpu_pubkeys_read.  d_in: out (out_len bytes per row: the staging buffer k_pk_table_read fills 16 bytes at a time).
+struct PubkeysRead {
+  size_t out, total;
+  PubkeysRead(size_t n, size_t out_len) {
+    Carve c;
+    out = c.take(n * out_len), total = c.end;
+  }
+};
+
 // blsgpu_signing_roots.  d_in: objects | domains (one per object, or one for all when domain_stride is 0) | roots.
 struct SigningRoots {
   size_t objects, dom, out, total, dom_bytes;

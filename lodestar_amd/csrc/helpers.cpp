@@ -864,6 +864,23 @@ int blsgpu_key_validate(blsgpu_ctx* ctx, uint32_t n, const uint8_t* pks, uint32_
   });
 }
 
+int blsgpu_pubkeys_read(blsgpu_ctx* ctx, uint32_t first_index, uint32_t n, uint8_t* out, uint32_t out_len) {
+  if (!ctx || ctx->devs.empty() || (out_len != 48 && out_len != 96)) return BLSGPU_ERR_ARGS;
+  if (n == 0) return BLSGPU_OK;
+  if (!out) return BLSGPU_ERR_ARGS;
+  return helper_call(ctx, true, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    if ((uint64_t)first_index + n > d.table_n) return BLSGPU_ERR_ARGS;
+    const hl::PubkeysRead l(n, out_len);
+    sl.d_in.ensure(l.total);
+    uint8_t* din = sl.d_in.p;
+    launch_pk_table_read(d.table.p, first_index, n, din + l.out, out_len, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, din + l.out, (size_t)n * out_len, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BLSGPU_OK;
+  });
+}
+
 int blsgpu_signing_roots(blsgpu_ctx* ctx, int kind, uint32_t n, const uint8_t* objects, uint32_t object_stride,
                          const uint8_t* domains, uint32_t domain_stride, uint8_t* out32) {
   if (!ctx || ctx->devs.empty() || !objects || !domains || !out32) return BLSGPU_ERR_ARGS;

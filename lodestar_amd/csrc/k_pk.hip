@@ -1,6 +1,10 @@
 // A4 PublicKey.aggregate (device pubkey table or per-key bytes), r_i * pk_i (A9), same-message unit sums,
-// aggregate serialization (PublicKey.aggregate(...).toBytes()), KeyValidate and the table upload decoder.
+// aggregate serialization (PublicKey.aggregate(...).toBytes()), KeyValidate, the table upload decoders (96-byte and
+// 48-byte compressed keys) and the table readback.
 #include "k_common.hpp"
+#include "pk_row.hpp"
+
+static_assert(PK_ROW_WORDS == W_PKTAB, "pk_row.hpp restates the row width of kernels.h");
 
 #ifndef BLSGPU_PK_AGG_GROUPS
 #define BLSGPU_PK_AGG_GROUPS 1
@@ -313,6 +317,55 @@ __global__ __launch_bounds__(WAVE) void k_pk_table_fill(const uint8_t* pk96, uin
   status[i] = (int8_t)st;
 }
 
+// The table upload from 48-byte compressed keys (blsgpu_pubkeys_upload_compressed), one lane per key: three 16-byte
+// loads of the key, pk_row_from48 (pk_row.hpp: the decompression's square root and, in the validate form only, the
+// subgroup check), eight 16-byte stores of the row -- the accesses of ld_pktab -- and the status byte.
+template <bool validate>
+__global__ __launch_bounds__(WAVE) void k_pk_table_fill48(const uint8_t* pk48, uint32_t n, uint32_t* table_dst,
+                                                          int8_t* status) {
+  const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+  if (i >= n) return;
+  uint8_t raw[48];
+  const uint4* src = reinterpret_cast<const uint4*>(pk48 + (size_t)i * 48);
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const uint4 v = src[k];
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 16; j++) raw[16 * k + j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+  }
+  uint32_t row[W_PKTAB];
+  const int st = pk_row_from48<validate>(raw, row);
+  uint4* dst = reinterpret_cast<uint4*>(table_dst + (size_t)i * W_PKTAB);
+#pragma unroll
+  for (int k = 0; k < W_PKTAB / 4; k++) dst[k] = make_uint4(row[4 * k], row[4 * k + 1], row[4 * k + 2], row[4 * k + 3]);
+  status[i] = (int8_t)st;
+}
+
+// Table readback (blsgpu_pubkeys_read), one lane per row: out[out_len k] = row first + k as 96 bytes (big-endian affine
+// x || y) or 48 (compressed), written 16 bytes at a time (both lengths are multiples of 16).  The caller keeps
+// first + n inside the table.
+__global__ __launch_bounds__(WAVE) void k_pk_table_read(const uint32_t* table, uint32_t first, uint32_t n, uint8_t* out,
+                                                        uint32_t out_len) {
+  const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+  if (i >= n) return;
+  const g1a a = ld_pktab(table, first + i);
+  uint8_t buf[96];
+  pk_point_to_bytes(a, out_len, buf);
+  uint4* dst = reinterpret_cast<uint4*>(out + (size_t)i * out_len);
+  const uint32_t quads = out_len / 16;
+#pragma unroll
+  for (uint32_t k = 0; k < 6; k++) {
+    if (k >= quads) break;
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      w[j] = (uint32_t)buf[16 * k + 4 * j] | (uint32_t)buf[16 * k + 4 * j + 1] << 8 |
+             (uint32_t)buf[16 * k + 4 * j + 2] << 16 | (uint32_t)buf[16 * k + 4 * j + 3] << 24;
+    dst[k] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+}
+
 static inline dim3 grid_for(uint32_t n) { return dim3((n + WAVE - 1) / WAVE); }
 
 // lanes per set: one wave per set while n sets leave SIMDs idle, else the fewest lanes (>= 8) that still give
@@ -346,4 +399,16 @@ void launch_key_validate(const uint8_t* pks, uint32_t n, uint32_t pk_len, uint32
 }
 void launch_pk_table_fill(const uint8_t* pk96, uint32_t n, uint32_t* table_dst, int8_t* status, hipStream_t s) {
   if (n) hipLaunchKernelGGL(k_pk_table_fill, grid_for(n), dim3(WAVE), 0, s, pk96, n, table_dst, status);
+}
+void launch_pk_table_fill48(const uint8_t* pk48, uint32_t n, uint32_t* table_dst, int8_t* status, bool validate,
+                            hipStream_t s) {
+  if (!n) return;
+  if (validate)
+    hipLaunchKernelGGL(k_pk_table_fill48<true>, grid_for(n), dim3(WAVE), 0, s, pk48, n, table_dst, status);
+  else
+    hipLaunchKernelGGL(k_pk_table_fill48<false>, grid_for(n), dim3(WAVE), 0, s, pk48, n, table_dst, status);
+}
+void launch_pk_table_read(const uint32_t* table, uint32_t first, uint32_t n, uint8_t* out, uint32_t out_len,
+                          hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_pk_table_read, grid_for(n), dim3(WAVE), 0, s, table, first, n, out, out_len);
 }

@@ -197,6 +197,13 @@ void launch_range_combine(const uint32_t* S_in, const uint32_t* F_in, uint32_t n
                           uint32_t n_out, uint32_t* S_out, uint32_t* F_out, hipStream_t s);
 // pubkey table upload: decode 96-byte affine encodings into table entries, per-entry status
 void launch_pk_table_fill(const uint8_t* pk96, uint32_t n, uint32_t* table_dst, int8_t* status, hipStream_t s);
+// the same from 48-byte compressed encodings (pk48 16-byte aligned): a row and a status per key, an all-zero row for a
+// rejected one; validate adds the G1 subgroup check (KeyValidate) to the decompression
+void launch_pk_table_fill48(const uint8_t* pk48, uint32_t n, uint32_t* table_dst, int8_t* status, bool validate,
+                            hipStream_t s);
+// table rows [first, first + n) -> out[out_len k] (16-byte aligned), out_len 96 (big-endian x || y) or 48 (compressed)
+void launch_pk_table_read(const uint32_t* table, uint32_t first, uint32_t n, uint8_t* out, uint32_t out_len,
+                          hipStream_t s);
 // serialize the per-set aggregate (pk_jac) to 96-byte uncompressed or 48-byte compressed encodings
 void launch_pk_serialize(const PipelineBuffers& b, uint32_t n_sets, uint8_t* out, uint32_t out_len, hipStream_t s);
 // KeyValidate of untrusted 48/96-byte pubkeys (decode + G1 subgroup check) -> 96-byte uncompressed

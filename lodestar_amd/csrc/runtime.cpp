@@ -775,10 +775,36 @@ uint32_t blsgpu_pubkeys_count(const blsgpu_ctx* ctx) {
   return n;
 }
 
-int blsgpu_pubkeys_upload(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* pk96, uint32_t n) {
-  if (!ctx) return BLSGPU_ERR_ARGS;
-  if (n == 0) return BLSGPU_OK;
-  if (!pk96) return BLSGPU_ERR_ARGS;
+}  // extern "C"
+
+namespace {
+
+// How one encoding fills table rows: `elem` bytes per key, and the launcher that decodes n keys at `src` (device) into
+// n rows at `rows` and a status byte per key (an all-zero row for a rejected key); `validate` is passed on to it.
+struct TableFill {
+  uint32_t elem;
+  void (*launch)(const uint8_t* src, uint32_t n, uint32_t* rows, int8_t* status, bool validate, hipStream_t s);
+  bool validate;
+};
+void fill_from96(const uint8_t* src, uint32_t n, uint32_t* rows, int8_t* status, bool, hipStream_t s) {
+  launch_pk_table_fill(src, n, rows, status, s);
+}
+
+// a device allocation of one upload, freed however the upload ends
+struct UploadTemp {
+  void* p = nullptr;
+  ~UploadTemp() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// The scaffold of both table uploads (n > 0, keys non-null): entries [first_index, first_index + n) of every device's
+// replica from keys[fill.elem k].  The call's value is the code of the lowest-index rejected key (nothing is written
+// then), BLSGPU_ERR_ARGS for a first_index beyond the table, BLSGPU_ERR_CLOSED / BLSGPU_DEVICE_ERROR.  Once the keys
+// were decoded, status (nullable, [n]) holds every key's code and *first_bad (nullable) the lowest rejected index or
+// 0xffffffff: the decode is the same on every device, device 0's is reported.
+int table_upload(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* keys, uint32_t n, const TableFill& fill,
+                 int8_t* status, uint32_t* first_bad) {
   if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
   std::lock_guard<std::mutex> tl(ctx->table_mu);
   int result = BLSGPU_OK;
@@ -788,25 +814,33 @@ int blsgpu_pubkeys_upload(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* 
   }
   // every device decodes and stores its own replica; the devices upload concurrently (one host thread each), so a
   // 2^20-key table on 8 GPUs costs one device's upload time, not eight
-  auto upload_one = [&](Device* d) -> int {
+  // (report: this device's statuses are the call's -- device 0)
+  auto upload_one = [&](Device* d, bool report) -> int {
     try {
       HIPCHK(hipSetDevice(d->id));
       hipStream_t ts = d->table_stream;
       const uint32_t need = first_index + n;
-      uint8_t* dpk = nullptr;
-      int8_t* dst = nullptr;
-      uint32_t* tmp = nullptr;
-      HIPCHK(hipMalloc((void**)&dpk, (size_t)n * 96));
-      HIPCHK(hipMalloc((void**)&dst, n));
-      HIPCHK(hipMalloc((void**)&tmp, (size_t)n * W_PKTAB * 4));
-      HIPCHK(hipMemcpyAsync(dpk, pk96, (size_t)n * 96, hipMemcpyHostToDevice, ts));
-      launch_pk_table_fill(dpk, n, tmp, dst, ts);
+      UploadTemp t_pk, t_st, t_rows;
+      HIPCHK(hipMalloc(&t_pk.p, (size_t)n * fill.elem));
+      HIPCHK(hipMalloc(&t_st.p, n));
+      HIPCHK(hipMalloc(&t_rows.p, (size_t)n * W_PKTAB * 4));
+      uint8_t* dpk = static_cast<uint8_t*>(t_pk.p);
+      int8_t* dst = static_cast<int8_t*>(t_st.p);
+      uint32_t* tmp = static_cast<uint32_t*>(t_rows.p);
+      HIPCHK(hipMemcpyAsync(dpk, keys, (size_t)n * fill.elem, hipMemcpyHostToDevice, ts));
+      fill.launch(dpk, n, tmp, dst, fill.validate, ts);
       HIPCHK(hipGetLastError());
       std::vector<int8_t> hst(n);
       HIPCHK(hipMemcpyAsync(hst.data(), dst, n, hipMemcpyDeviceToHost, ts));
       HIPCHK(hipStreamSynchronize(ts));
       int err = 0;
-      for (uint32_t i = 0; i < n && !err; i++) err = hst[i];
+      uint32_t bad = 0xffffffffu;
+      for (uint32_t i = 0; i < n && !err; i++)
+        if (hst[i]) err = hst[i], bad = i;
+      if (report) {
+        if (status) memcpy(status, hst.data(), n);
+        if (first_bad) *first_bad = bad;
+      }
       if (!err) {
         std::unique_lock<std::shared_mutex> lk(d->table_mu);
         if (need > d->table.cap / W_PKTAB) {
@@ -823,9 +857,6 @@ int blsgpu_pubkeys_upload(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* 
         HIPCHK(hipStreamSynchronize(ts));
         d->table_n = std::max(d->table_n, need);
       }
-      (void)hipFree(dpk);
-      (void)hipFree(dst);
-      (void)hipFree(tmp);
       return err;
     } catch (HipError&) {
       return BLSGPU_DEVICE_ERROR;
@@ -836,10 +867,11 @@ int blsgpu_pubkeys_upload(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* 
   if (!result) {
     std::vector<int> rc(ctx->devs.size(), 0);
     if (ctx->devs.size() == 1) {
-      rc[0] = upload_one(ctx->devs[0]);
+      rc[0] = upload_one(ctx->devs[0], true);
     } else {
       std::vector<std::thread> th;
-      for (size_t k = 0; k < ctx->devs.size(); k++) th.emplace_back([&, k] { rc[k] = upload_one(ctx->devs[k]); });
+      for (size_t k = 0; k < ctx->devs.size(); k++)
+        th.emplace_back([&, k] { rc[k] = upload_one(ctx->devs[k], k == 0); });
       for (auto& t : th) t.join();
     }
     for (int r : rc)
@@ -847,6 +879,26 @@ int blsgpu_pubkeys_upload(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* 
   }
   leave(ctx);
   return result;
+}
+
+}  // namespace
+
+extern "C" {
+
+int blsgpu_pubkeys_upload(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* pk96, uint32_t n) {
+  if (!ctx) return BLSGPU_ERR_ARGS;
+  if (n == 0) return BLSGPU_OK;
+  if (!pk96) return BLSGPU_ERR_ARGS;
+  return table_upload(ctx, first_index, pk96, n, TableFill{96, fill_from96, false}, nullptr, nullptr);
+}
+
+int blsgpu_pubkeys_upload_compressed(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* pk48, uint32_t n,
+                                     uint32_t flags, int8_t* status, uint32_t* first_bad) {
+  if (!ctx || (flags & ~BLSGPU_PK_VALIDATE)) return BLSGPU_ERR_ARGS;
+  if (n == 0) return BLSGPU_OK;
+  if (!pk48 || (uint64_t)first_index + n > 0xffffffffull) return BLSGPU_ERR_ARGS;
+  const TableFill fill{48, launch_pk_table_fill48, (flags & BLSGPU_PK_VALIDATE) != 0};
+  return table_upload(ctx, first_index, pk48, n, fill, status, first_bad);
 }
 
 // The options of the table (options.hpp kOptionRows) are stored in ctx->opt under opt_mu; the keys that live on the

@@ -64,7 +64,10 @@ EXPORTED_SYMBOLS = [
     "blsgpu_aggregate_verify_form",
     "blsgpu_verify_same_message_agg",
     "blsgpu_same_message_agg_lanes",
+    "blsgpu_pubkeys_upload_compressed",
+    "blsgpu_pubkeys_read",
 ]
+PK_VALIDATE = 1  # BLSGPU_PK_VALIDATE: the uploaded keys are untrusted, KeyValidate each
 SAME_LANE_FORMS = 1
 SAME_BLOCK_CHECK = 4  # BLSGPU_SAME_BLOCK_CHECK: one check per block of 1024 groups, then the descent
 # blsgpu_aggregate_verify flags
@@ -223,6 +226,10 @@ def load():
     lib.blsgpu_aggregate_verify.restype = ctypes.c_int
     lib.blsgpu_aggregate_verify_form.argtypes = [u32, u32]
     lib.blsgpu_aggregate_verify_form.restype = u32
+    lib.blsgpu_pubkeys_upload_compressed.argtypes = [vp, u32, vp, u32, u32, vp, vp]
+    lib.blsgpu_pubkeys_upload_compressed.restype = ctypes.c_int
+    lib.blsgpu_pubkeys_read.argtypes = [vp, u32, u32, vp, u32]
+    lib.blsgpu_pubkeys_read.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -509,6 +516,32 @@ class Context:
         rc = self._lib.blsgpu_pubkeys_upload(self.h, first_index, pk96, n)
         if rc != OK:
             raise ValueError(f"blsgpu_pubkeys_upload -> {code_name(rc)}")
+
+    def upload_pubkeys_compressed(self, first_index: int, pk48: bytes, validate=False):
+        """Table entries [first_index, first_index + n) from 48-byte compressed keys, decompressed on the GPU (validate:
+        KeyValidate each, BLSGPU_PK_VALIDATE).  Returns (status int8 array, first_bad): a rejected key is reported --
+        status[k] its code, first_bad the lowest rejected index, nothing stored -- not raised; first_bad is 0xffffffff
+        when every key was stored.  Raises only for a call-level failure (BLSGPU_ERR_*, DEVICE_ERROR)."""
+        src = _u8(pk48)
+        if len(src) % 48:
+            raise ValueError("48-byte compressed pubkeys expected")
+        n = len(src) // 48
+        st = np.zeros(max(n, 1), np.int8)
+        fb = ctypes.c_uint32(0xFFFFFFFF)
+        rc = self._lib.blsgpu_pubkeys_upload_compressed(self.h, first_index, src.ctypes.data if n else None, n,
+                                                        PK_VALIDATE if validate else 0, st.ctypes.data,
+                                                        ctypes.byref(fb))
+        if rc >= 100 or rc == DEVICE_ERROR:
+            raise RuntimeError(f"blsgpu_pubkeys_upload_compressed -> {code_name(rc)}")
+        return st[:n], fb.value
+
+    def read_pubkeys(self, first_index: int, n: int, out_len=96) -> bytes:
+        """Table entries [first_index, first_index + n) as 96-byte uncompressed or 48-byte compressed encodings."""
+        out = np.zeros(max(n * out_len, 1), np.uint8)
+        rc = self._lib.blsgpu_pubkeys_read(self.h, first_index, n, out.ctypes.data, out_len)
+        if rc != OK:
+            raise RuntimeError(f"blsgpu_pubkeys_read -> {code_name(rc)}")
+        return out[: n * out_len].tobytes()
 
     @property
     def pubkeys_count(self):

@@ -136,6 +136,30 @@ class BlsGpuVerifier {
     addon.uploadPubkeys(this.ctx, firstIndex, pk96);
   }
 
+  /**
+   * The same sync from what the state holds: entries [firstIndex, firstIndex + n) from 48-byte compressed keys
+   * (state.validators[i].pubkey concatenated), decompressed on the device.  The keys are trusted, as pubkeyCache.ts
+   * trusts the state's; {validate: true} runs KeyValidate on each.  A rejected key throws "BLST_ERROR: <NAME>" with
+   * .index its validator index; nothing is stored then.
+   */
+  uploadPubkeysCompressed(firstIndex, pk48, opts = {}) {
+    const r = addon.uploadPubkeysCompressed(this.ctx, firstIndex, pk48, !!opts.validate);
+    if (r.firstBad !== 0xffffffff) {
+      const e = jobError(r.status[r.firstBad]);
+      e.index = firstIndex + r.firstBad;
+      throw e;
+    }
+  }
+
+  /**
+   * Entries [firstIndex, firstIndex + n) of the device table as a Buffer of 96-byte uncompressed encodings (what
+   * PublicKey.fromBytes takes without a square root: index2pubkey can be hydrated from it) or, with
+   * {compressed: true}, 48-byte compressed ones.
+   */
+  readPubkeys(firstIndex, n, opts = {}) {
+    return addon.readPubkeys(this.ctx, firstIndex, n, opts.compressed ? 48 : 96);
+  }
+
   registerPubkey(obj, index) {
     this.pkIndexOf.set(obj, index);
   }

@@ -11,6 +11,11 @@
  *   close(ctx)                                                    blsgpu_destroy  (IBlsVerifier.close)
  *   deviceCount(ctx) -> number                                    blsgpu_device_count
  *   uploadPubkeys(ctx, firstIndex, Uint8Array 96*n)               blsgpu_pubkeys_upload (index2pubkey)
+ *   uploadPubkeysCompressed(ctx, firstIndex, Uint8Array 48*n, validate) -> {status: Int8Array, firstBad: number}
+ *     blsgpu_pubkeys_upload_compressed (synchronous; state.validators[i].pubkey as it is, decompressed on the device):
+ *     a rejected key is reported (status[k] its blst code, firstBad the lowest rejected index, nothing stored;
+ *     firstBad 0xffffffff = all stored), only a call-level code throws
+ *   readPubkeys(ctx, firstIndex, n, outLen 48|96) -> Buffer       blsgpu_pubkeys_read (synchronous)
  *   pubkeysCount(ctx) -> number                                   blsgpu_pubkeys_count
  *   setOption(ctx, key, value)                                    blsgpu_set_option
  *   codeName(code) -> string                                      blsgpu_code_name
@@ -222,6 +227,74 @@ static napi_value UploadPubkeys(napi_env env, napi_callback_info info) {
   int rc = blsgpu_pubkeys_upload(box->ctx, first, (const uint8_t*)data, (uint32_t)(len / 96));
   if (rc != BLSGPU_OK) return throw_code(env, "uploadPubkeys", rc);
   return NULL;
+}
+
+/* uploadPubkeysCompressed(ctx, firstIndex, Uint8Array 48*n, validate) -> {status: Int8Array, firstBad}  (synchronous) */
+static napi_value UploadPubkeysCompressed(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 3) {
+    napi_throw_type_error(env, NULL, "uploadPubkeysCompressed(ctx, firstIndex, pk48, validate)");
+    return NULL;
+  }
+  CtxBox* box = get_open_box(env, argv[0]);
+  if (!box) return NULL;
+  uint32_t first;
+  CHECK(env, napi_get_value_uint32(env, argv[1], &first));
+  napi_typedarray_type type;
+  size_t len = 0;
+  void* data = NULL;
+  if (napi_get_typedarray_info(env, argv[2], &type, &len, &data, NULL, NULL) != napi_ok || type != napi_uint8_array ||
+      len % 48) {
+    napi_throw_type_error(env, NULL, "uploadPubkeysCompressed: expected a Uint8Array of 48-byte compressed pubkeys");
+    return NULL;
+  }
+  bool validate = false;
+  if (argc >= 4) napi_coerce_to_bool(env, argv[3], &argv[3]), napi_get_value_bool(env, argv[3], &validate);
+  uint32_t n = (uint32_t)(len / 48), first_bad = 0xffffffffu;
+  napi_value ab_st, st, fb, out;
+  void* p_st = NULL;
+  CHECK(env, napi_create_arraybuffer(env, n ? n : 1, &p_st, &ab_st));
+  memset(p_st, 0, n ? n : 1);
+  int rc = blsgpu_pubkeys_upload_compressed(box->ctx, first, (const uint8_t*)data, n, validate ? BLSGPU_PK_VALIDATE : 0,
+                                            (int8_t*)p_st, &first_bad);
+  if (rc >= BLSGPU_ERR_ARGS || rc == BLSGPU_DEVICE_ERROR) return throw_code(env, "uploadPubkeysCompressed", rc);
+  CHECK(env, napi_create_typedarray(env, napi_int8_array, n, ab_st, 0, &st));
+  CHECK(env, napi_create_uint32(env, first_bad, &fb));
+  CHECK(env, napi_create_object(env, &out));
+  napi_set_named_property(env, out, "status", st);
+  napi_set_named_property(env, out, "firstBad", fb);
+  return out;
+}
+
+/* readPubkeys(ctx, firstIndex, n, outLen 48|96) -> Buffer of n * outLen bytes  (synchronous) */
+static napi_value ReadPubkeys(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 4) {
+    napi_throw_type_error(env, NULL, "readPubkeys(ctx, firstIndex, n, outLen)");
+    return NULL;
+  }
+  CtxBox* box = get_open_box(env, argv[0]);
+  if (!box) return NULL;
+  uint32_t first = 0, n = 0, out_len = 0;
+  CHECK(env, napi_get_value_uint32(env, argv[1], &first));
+  CHECK(env, napi_get_value_uint32(env, argv[2], &n));
+  CHECK(env, napi_get_value_uint32(env, argv[3], &out_len));
+  if (out_len != 48 && out_len != 96) {
+    napi_throw_range_error(env, "BLSGPU_ERR_ARGS", "readPubkeys: outLen must be 48 or 96");
+    return NULL;
+  }
+  /* the range is checked before anything of its size is allocated (the library checks it again under its lock) */
+  if (n && (uint64_t)first + n > blsgpu_pubkeys_count(box->ctx)) return throw_code(env, "readPubkeys", BLSGPU_ERR_ARGS);
+  napi_value buf;
+  void* p = NULL;
+  CHECK(env, napi_create_buffer(env, (size_t)n * out_len, &p, &buf));
+  int rc = blsgpu_pubkeys_read(box->ctx, first, n, (uint8_t*)p, out_len);
+  if (rc != BLSGPU_OK) return throw_code(env, "readPubkeys", rc);
+  return buf;
 }
 
 static napi_value PubkeysCount(napi_env env, napi_callback_info info) {
@@ -1139,6 +1212,8 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
       {"close", NULL, Close, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"deviceCount", NULL, DeviceCount, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"uploadPubkeys", NULL, UploadPubkeys, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
+      {"uploadPubkeysCompressed", NULL, UploadPubkeysCompressed, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
+      {"readPubkeys", NULL, ReadPubkeys, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"pubkeysCount", NULL, PubkeysCount, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"setOption", NULL, SetOption, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"getOption", NULL, GetOption, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},

@@ -147,6 +147,12 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
   close(): Promise<void>;
   /** index2pubkey sync: entries [firstIndex, firstIndex + n) as 96-byte uncompressed encodings. */
   uploadPubkeys(firstIndex: number, pk96: Uint8Array): void;
+  /** The same sync from 48-byte compressed keys (state.validators[i].pubkey concatenated), decompressed on the device;
+   * trusted unless {validate: true} (KeyValidate each).  A rejected key throws "BLST_ERROR: <NAME>" with .index its
+   * validator index; nothing is stored then. */
+  uploadPubkeysCompressed(firstIndex: number, pk48: Uint8Array, opts?: {validate?: boolean}): void;
+  /** entries [firstIndex, firstIndex + n) of the device table: 96-byte uncompressed encodings, or 48-byte compressed */
+  readPubkeys(firstIndex: number, n: number, opts?: {compressed?: boolean}): Buffer;
   /** maps a PublicKey object (by identity) to its validator index in the device table */
   registerPubkey(pk: object, index: number): void;
   readonly deviceCount: number;
