@@ -567,6 +567,19 @@ const char* blsgpu_code_name(int code);
  *     18 lane-pair G2 arithmetic (fp2x.hpp) against the one-lane forms: P, Q affine (384) -> [|z|]P affine (192);
  *        status = bitmask of the cases (add, add doubling / infinity branches, dbl, mixed add, psi, psi^2, [|z|],
  *        Fp2 product / square) where the lane-pair result differs
+ *     32..68 the field tower on raw limbs (csrc/tower_debug.hpp; 14 LE 28-bit limb words = 56 bytes per Fp value,
+ *        k x 56 -> m x 56, nothing converted or reduced on the way in; 128-lane workgroups; strides multiples of 4,
+ *        out_stride > 0), [k -> m] in Fp values:
+ *        32 fp_mul [2->1] 33 fp_sqr [1->1] 34 fp2_mul [4->2] 35 fp2_sqr [2->2] 36 fp2_mul_fp [3->2]
+ *        37 fp_add 38 fp_sub [2->1] 39 fp_neg 40 fp_dbl 41 fp_half 42 fp_mul3 43 fp_mul4 44 fp_mul8 45 fp_canon [1->1]
+ *        46 fp_add_norm [2->1] 47 fp2_mul_xi [2->2]
+ *        48 fp_is_zero [1->0] 49 fp_eq [2->0] 50 fp12_is_one [12->0]: status = the answer (1 / 0)
+ *        51 fp_inv 52 fp_pow_p34 [1->1] 53 fp2_inv [2->2] 54 fp6_inv [6->6] 55 fp12_inv [12->12]
+ *        56 fp2_sqrt [2->2]: status = the returned flag
+ *        57 fp6_mul [12->6] 58 fp6_mul_by_01 (x, l0, l1) [10->6] 59 fp6_mul_by_12 (a, b1, b2) [10->6]
+ *        60 fp12_mul [24->12] 61 fp12_sqr [12->12] 62 fp12_mul_by_014 (f, l0, l1, l4) [18->12]
+ *        63 fp12_mul_by_line2(f, line_pair(a0, a1, a4, b0, b1, b4)) [24->12] 64 fp12_frob1 65 fp12_frob2
+ *        66 fp12_conj 67 fp12_pow_zabs 68 fp12_cyclotomic_sqr [12->12]
  * Strides below an op's element size, and unknown ops, are refused with BLSGPU_ERR_ARGS.
  * Returns BLSGPU_OK or an error. */
 int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint32_t in_stride,

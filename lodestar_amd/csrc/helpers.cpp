@@ -912,11 +912,21 @@ int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint
   };
   static const OpSize kOpSizes[] = {{0, 96, 48},    {1, 194, 192},  {2, 32, 192},   {3, 288, 576},  {4, 576, 576},
                                     {5, 104, 96},   {6, 200, 192},  {7, 64, 96},    {8, 32, 96},    {9, 200, 2880},
-                                    {10, 104, 1440}, {11, 840, 56}, {16, 576, 576}, {17, 288, 576}, {18, 384, 192}};
+                                    {10, 104, 1440}, {11, 840, 56}, {16, 576, 576}, {17, 288, 576}, {18, 384, 192},
+      // the field tower's raw-limb hooks (tower_debug.hpp): 56 bytes per Fp value in and out, predicates write nothing
+      {32, 112, 56}, {33, 56, 56}, {34, 224, 112}, {35, 112, 112}, {36, 168, 112}, {37, 112, 56},
+      {38, 112, 56}, {39, 56, 56}, {40, 56, 56}, {41, 56, 56}, {42, 56, 56}, {43, 56, 56},
+      {44, 56, 56}, {45, 56, 56}, {46, 112, 56}, {47, 112, 112}, {48, 56, 0}, {49, 112, 0},
+      {50, 672, 0}, {51, 56, 56}, {52, 56, 56}, {53, 112, 112}, {54, 336, 336}, {55, 672, 672},
+      {56, 112, 112}, {57, 672, 336}, {58, 560, 336}, {59, 560, 336}, {60, 1344, 672}, {61, 672, 672},
+      {62, 1008, 672}, {63, 1344, 672}, {64, 672, 672}, {65, 672, 672}, {66, 672, 672}, {67, 672, 672},
+      {68, 672, 672}};
   const OpSize* sz = nullptr;
   for (const OpSize& o : kOpSizes)
     if (o.op == op) sz = &o;
   if (!sz || in_stride < sz->in || out_stride < sz->out) return BLSGPU_ERR_ARGS;
+  const bool tower = op >= 32;  // limb words are read and written as uint32: word-aligned elements only
+  if (tower && (in_stride % 4 || out_stride % 4 || out_stride == 0)) return BLSGPU_ERR_ARGS;
   if (n == 0) return BLSGPU_OK;
   return helper_call(ctx, false, [&](Device& d, Slot& sl, hipStream_t s) -> int {
     struct Temp {  // its own allocations, not the helper's arenas: freed however the call ends
@@ -930,7 +940,10 @@ int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint
     HIPCHK(hipMalloc(&dst.p, (size_t)n * 4));
     HIPCHK(hipMemcpyAsync(din.p, in, (size_t)n * in_stride, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(dout.p, 0, (size_t)n * out_stride, s));
-    launch_debug_op(op, n, (uint8_t*)din.p, in_stride, (uint8_t*)dout.p, out_stride, (int32_t*)dst.p, s);
+    if (tower)
+      launch_debug_tower(op, n, (uint8_t*)din.p, in_stride, (uint8_t*)dout.p, out_stride, (int32_t*)dst.p, s);
+    else
+      launch_debug_op(op, n, (uint8_t*)din.p, in_stride, (uint8_t*)dout.p, out_stride, (int32_t*)dst.p, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * out_stride, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(status, dst.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));

@@ -381,3 +381,6 @@ void launch_signing_roots(int kind, const uint8_t* in, uint32_t n, uint32_t in_s
 // debug ops (blsgpu_debug_op)
 void launch_debug_op(int op, uint32_t n, const uint8_t* in, uint32_t in_stride, uint8_t* out, uint32_t out_stride,
                      int32_t* status, hipStream_t s);
+// the field tower's raw-limb hooks (ops 32..68, tower_debug.hpp): 128-lane workgroups, strides multiples of 4
+void launch_debug_tower(int op, uint32_t n, const uint8_t* in, uint32_t in_stride, uint8_t* out, uint32_t out_stride,
+                        int32_t* status, hipStream_t s);

@@ -30,7 +30,7 @@ BLS_HD fp2 fp2_add_nr(const fp2& a, const fp2& b) { return fp2_make(fp_add_nr(a.
 BLS_HD fp2 fp2_add_norm(const fp2& a, const fp2& b) { return fp2_make(fp_add_norm(a.c0, b.c0), fp_add_norm(a.c1, b.c1)); }
 
 // 64 p^2 in 28 limbs of 28 bits: the multiple of p added to a0 b0 - a1 b1 in fp2_mul_lazy_body so the c0 column sum
-// stays a non-negative integer for inputs < 8p (a1 b1 < 64 p^2)
+// stays a non-negative integer for inputs <= 8p (a1 b1 <= 64 p^2)
 BLS_CONST uint32_t FP2_LAZY_OFS[2 * BLS_NL] = {
     0xc638e40, 0x8000071, 0xbaac9aa, 0xc75d8e0, 0xf5f3b5a, 0xd8844f3, 0x58b0ce0, 0x9c6dd0c, 0xfe47b4f, 0x681259a,
     0x16a1c24, 0x1eca4ba, 0x7218617, 0x475a186, 0x25e3bc0, 0x4c524cc, 0x7729bbd, 0x8b3f45b, 0x2f41429, 0x924d27a,
@@ -40,9 +40,10 @@ BLS_CONST uint32_t FP2_LAZY_OFS[2 * BLS_NL] = {
 // (a0 b0, a1 b1, (a0 + a1)(b0 + b1), column sums only) interleaved column by column:
 //   c0 = Redc(a0 b0 - a1 b1 + 64 p^2),   c1 = Redc((a0 + a1)(b0 + b1) - a0 b0 - a1 b1)
 // 5 x 196 = 980 v_mad_u64_u32 instead of 3 x 392, and five independent MAD chains per column instead of one.
-// Inputs: limbs < 2^29 (normalized values or one fp_add_nr level), values < 8p.  Column bounds: t0, t1 < 14 * 2^58,
-// t2 < 14 * 2^60 (the limb sums a0_i + a1_i < 2^30 are not normalized); t2 - t0 - t1 is exactly the cross-term
-// column sum(a0_i b1_j + a1_i b0_j) >= 0; t0 - t1 + ofs may be negative, so c0 runs on a signed accumulator with
+// Inputs: limbs < 2^29 (normalized values or one fp_add_nr level), values <= 8p (8p itself included: fp6_mul hands it
+// the un-normalized sum 4p + 4p; tests/tower_vectors.py pins that edge on the host and the device).
+// Column bounds: t0, t1 < 14 * 2^58, t2 < 14 * 2^60 (the limb sums a0_i + a1_i < 2^30 are not normalized); t2 - t0 - t1
+// is exactly the cross-term column sum(a0_i b1_j + a1_i b0_j) >= 0; t0 - t1 + ofs may be negative, so c0 runs on a signed accumulator with
 // arithmetic shifts (|acc0| < 2^63).  Outputs: normalized limbs, values < 1.06 p.
 BLS_INL fp2 fp2_mul_lazy_body(const fp& a0, const fp& a1, const fp& b0, const fp& b1) {
   uint32_t s[BLS_NL], u[BLS_NL], m0[BLS_NL], m1[BLS_NL];
@@ -91,14 +92,14 @@ BLS_INL fp2 fp2_mul_lazy_body(const fp& a0, const fp& a1, const fp& b0, const fp
 }
 
 // 16p with limbs 0-12 borrowed up into [2^29, 2^30): 16p - b has no negative limb for b with limbs < 2^29 and a top
-// limb below 0x1a010e (values < 8p, normalized or one fp_add_nr level)
+// limb below 0x1a010e (values <= 8p, normalized or one fp_add_nr level)
 BLS_CONST fp FP_16P_K = {{0x3ffaaab0, 0x3efffffc, 0x3ffffb9c, 0x3ffeb150, 0x3241eabc, 0x30f6b0f3, 0x36730d27, 0x338512bc,
                           0x3774b84c, 0x3bacd761, 0x3a7b6431, 0x369a4b18, 0x3ea397fb, 0x001a010e}};
 // Fp2 product as two schoolbook column sums straight into the two Montgomery accumulators, no Karatsuba
 // recombination: c0 = Redc(a0 b0 + a1 (16p - b1)) (= a0 b0 - a1 b1 mod p), c1 = Redc(a0 b1 + a1 b0).  784 + 392
 // v_mad_u64_u32 against the lazy body's 980, but no 64-bit column subtractions (with their carry hazards), no signed
 // accumulator and no operand sums: fewer instruction slots and registers per product.  Inputs as fp2_mul_lazy_body
-// (limbs < 2^29, values < 8p); column bound 14 (2^58 + 2^59) + 14 * 2^56 + 2^36 < 2^64; outputs normalized, < 1.1 p.
+// (limbs < 2^29, values <= 8p); column bound 14 (2^58 + 2^59) + 14 * 2^56 + 2^36 < 2^64; outputs normalized, < 1.1 p.
 BLS_INL fp2 fp2_mul_sb_body(const fp& a0, const fp& a1, const fp& b0, const fp& b1) {
   uint32_t nb[BLS_NL], m0[BLS_NL], m1[BLS_NL];
 #pragma unroll
@@ -224,7 +225,8 @@ __device__ __forceinline__ fp2 fp2_mul(const fp2& a, const fp2& b) {
   return fp2_from_ret(fp2_mul_r(BLS_ARGS14(a.c0), BLS_ARGS14(a.c1)));
 }
 __device__ __forceinline__ fp2 fp2_sqr(const fp2& a) { return fp2_from_ret(fp2_sqr_r(BLS_ARGS14(a.c0), BLS_ARGS14(a.c1))); }
-// a * s (s in Fp, through the LDS slot): two interleaved products in one call
+// a * s (s in Fp, through the LDS slot): two interleaved products in one call.  a.c0, a.c1 and s are fp_mul operands
+// (limbs < 2^30, values < 16p); outputs normalized, < p + a_k s / 2^392
 __device__ __noinline__ fp2_ret fp2_mul_fp_r(BLS_PARAMS14(a), BLS_PARAMS14(c)) {
   const fp x0 = BLS_INIT14(a), x1 = BLS_INIT14(c);
   const uint32_t t = threadIdx.x;
@@ -614,6 +616,7 @@ BLS_FN fp12 line_pair(const fp2& a0, const fp2& a1, const fp2& a4, const fp2& b0
 
 // f * m with m.c1.c0 = 0 (a line_pair product): Karatsuba over Fp6, t1 = f1 m1 with m1 = (0, b1, b2) in five
 // products: c0 = xi (X - t1 - t2), c1 = (a0 + a1) b1 - t1 + xi t2, c2 = (a0 + a2) b2 - t2 + t1, X = (a1 + a2)(b1 + b2)
+// (a, b1, b2 normalized, values <= 4p: the un-normalized sums reach fp2_mul's 8p; outputs fp_lc's, < 1.003 p)
 BLS_FN fp6 fp6_mul_by_12(const fp6& a, const fp2& b1, const fp2& b2) {
   const fp2 t1 = fp2_mul(a.c1, b1), t2 = fp2_mul(a.c2, b2);
   fp6 r;

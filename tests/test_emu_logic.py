@@ -1,5 +1,8 @@
 """The device arithmetic (lodestar_amd/csrc/*.hpp), compiled for the host CPU by tests/native/emu.cpp,
-checked against the oracle.  Same source as the HIP kernels; the GPU parity tests re-check it on MI355X."""
+checked against the oracle.  Same source as the HIP kernels.  On MI355X the whole operations are re-checked by the
+GPU parity tests (tests/test_gpu_pipeline.py, tests/test_gpu_parity.py) and the operand contracts of the field tower
+by tests/test_gpu_tower_contracts.py, which runs the records of tests/tower_vectors.py (on the host:
+tests/test_tower_contracts.py) through the device build of these headers."""
 import ctypes
 import random
 
