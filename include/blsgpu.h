@@ -580,6 +580,19 @@ const char* blsgpu_code_name(int code);
  *        60 fp12_mul [24->12] 61 fp12_sqr [12->12] 62 fp12_mul_by_014 (f, l0, l1, l4) [18->12]
  *        63 fp12_mul_by_line2(f, line_pair(a0, a1, a4, b0, b1, b4)) [24->12] 64 fp12_frob1 65 fp12_frob2
  *        66 fp12_conj 67 fp12_pow_zabs 68 fp12_cyclotomic_sqr [12->12]
+ *     69..107 the one-lane point formulas on raw limbs (csrc/curve_debug.hpp; the same 56-byte Fp values, launch
+ *        shape and stride rule): a Jacobian point J = (x, y, z), an affine point A = (x, y); G1 coordinates are one Fp
+ *        value, G2 coordinates two (c0, c1).  G1 at 69 + s, G2 at 86 + s, [k -> m] in coordinates:
+ *        s = 0 jac_dbl 1 jac_dbl_lazy 2 jac_dbl_eager [J -> J: 3->3]
+ *        3 jac_add 4 jac_add_lazy 5 jac_add_eager [J, J -> J: 6->3]
+ *        6 jac_add_aff 7 jac_add_aff_lazy 8 jac_add_aff_eager [J, A -> J: 5->3]
+ *        9 jac_neg [3->3] 10 jac_is_inf [3->0] 11 jac_eq [6->0]: status = the answer
+ *        12 jac_to_aff [3->2]: status = the returned flag, A written only when it is 1
+ *        13 endo_lambda [3->3] 14 jac_mul_zabs [3->3]
+ *        84 g1_on_curve 85 g1_in_subgroup [A: 2->0], status = the answer
+ *        101 g2_psi 102 g2_psi2 103 jac_mul_zabs_ld [J -> J: 3->3] 104 jac_mul_zabs_lda [A -> J: 2->3] (the loaders
+ *        read the element's input words at every call) 105 g2_on_curve 106 g2_in_subgroup 107 g2_in_subgroup_ld
+ *        [A: 2->0], status = the answer
  * Strides below an op's element size, and unknown ops, are refused with BLSGPU_ERR_ARGS.
  * Returns BLSGPU_OK or an error. */
 int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint32_t in_stride,

@@ -920,7 +920,15 @@ int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint
       {50, 672, 0}, {51, 56, 56}, {52, 56, 56}, {53, 112, 112}, {54, 336, 336}, {55, 672, 672},
       {56, 112, 112}, {57, 672, 336}, {58, 560, 336}, {59, 560, 336}, {60, 1344, 672}, {61, 672, 672},
       {62, 1008, 672}, {63, 1344, 672}, {64, 672, 672}, {65, 672, 672}, {66, 672, 672}, {67, 672, 672},
-      {68, 672, 672}};
+      {68, 672, 672},
+      // the point formulas' hooks (curve_debug.hpp): Jacobian (x, y, z) / affine (x, y), G1 69..85, G2 86..107
+      {69, 168, 168}, {70, 168, 168}, {71, 168, 168}, {72, 336, 168}, {73, 336, 168}, {74, 336, 168},
+      {75, 280, 168}, {76, 280, 168}, {77, 280, 168}, {78, 168, 168}, {79, 168, 0}, {80, 336, 0},
+      {81, 168, 112}, {82, 168, 168}, {83, 168, 168}, {84, 112, 0}, {85, 112, 0},
+      {86, 336, 336}, {87, 336, 336}, {88, 336, 336}, {89, 672, 336}, {90, 672, 336}, {91, 672, 336},
+      {92, 560, 336}, {93, 560, 336}, {94, 560, 336}, {95, 336, 336}, {96, 336, 0}, {97, 672, 0},
+      {98, 336, 224}, {99, 336, 336}, {100, 336, 336}, {101, 336, 336}, {102, 336, 336}, {103, 336, 336},
+      {104, 224, 336}, {105, 224, 0}, {106, 224, 0}, {107, 224, 0}};
   const OpSize* sz = nullptr;
   for (const OpSize& o : kOpSizes)
     if (o.op == op) sz = &o;
@@ -940,7 +948,9 @@ int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint
     HIPCHK(hipMalloc(&dst.p, (size_t)n * 4));
     HIPCHK(hipMemcpyAsync(din.p, in, (size_t)n * in_stride, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(dout.p, 0, (size_t)n * out_stride, s));
-    if (tower)
+    if (op >= 69)  // (curve_debug.hpp CRV_OP_FIRST)
+      launch_debug_curve(op, n, (uint8_t*)din.p, in_stride, (uint8_t*)dout.p, out_stride, (int32_t*)dst.p, s);
+    else if (tower)
       launch_debug_tower(op, n, (uint8_t*)din.p, in_stride, (uint8_t*)dout.p, out_stride, (int32_t*)dst.p, s);
     else
       launch_debug_op(op, n, (uint8_t*)din.p, in_stride, (uint8_t*)dout.p, out_stride, (int32_t*)dst.p, s);

@@ -384,3 +384,6 @@ void launch_debug_op(int op, uint32_t n, const uint8_t* in, uint32_t in_stride, 
 // the field tower's raw-limb hooks (ops 32..68, tower_debug.hpp): 128-lane workgroups, strides multiples of 4
 void launch_debug_tower(int op, uint32_t n, const uint8_t* in, uint32_t in_stride, uint8_t* out, uint32_t out_stride,
                         int32_t* status, hipStream_t s);
+// the point formulas' raw-limb hooks (ops 69..107, curve_debug.hpp): the same launch shape and stride rule
+void launch_debug_curve(int op, uint32_t n, const uint8_t* in, uint32_t in_stride, uint8_t* out, uint32_t out_stride,
+                        int32_t* status, hipStream_t s);

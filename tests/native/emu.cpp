@@ -8,6 +8,7 @@
 #include "../../lodestar_amd/csrc/g2_coop.hpp"
 #include "../../lodestar_amd/csrc/gt_wave.hpp"
 #include "../../lodestar_amd/csrc/tower_debug.hpp"
+#include "../../lodestar_amd/csrc/curve_debug.hpp"
 
 #if defined(BLS_COUNT_OPS)
 unsigned long long bls_count_mul = 0, bls_count_sqr = 0, bls_count_half = 0;
@@ -515,3 +516,5 @@ extern "C" void emu_fp2_mul_sb_limbs(const uint32_t* in56, uint32_t* out28) {
 // operands and results as 14 limb words per Fp value, nothing converted or reduced on the way in -- the entry
 // tests/test_tower_contracts.py drives with every record of tests/tower_vectors.py.  Returns the status word.
 extern "C" int emu_tower_op(int op, const uint32_t* in, uint32_t* out) { return tower_debug_op(op, in, out); }
+// The point formulas' hooks (curve_debug.hpp, ops 69..107; tests/test_curve_contracts.py, tests/curve_vectors.py).
+extern "C" int emu_curve_op(int op, const uint32_t* in, uint32_t* out) { return curve_debug_op(op, in, out); }

@@ -78,12 +78,17 @@ def test_vector_set_shape():
 
 
 def test_op_sizes_match_the_library_table():
-    """blsgpu_debug_op's kOpSizes rows (helpers.cpp) for the tower ops are the vectors' operand / result counts at 56
-    bytes per Fp value, so a short stride is refused on the host."""
+    """blsgpu_debug_op's kOpSizes rows (helpers.cpp) for the tower ops and the point-formula ops (tests/curve_vectors.py)
+    are the vectors' operand / result counts at 56 bytes per Fp value, so a short stride is refused on the host."""
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lodestar_amd", "csrc",
                             "helpers.cpp")).read()
     table = src[src.index("kOpSizes[] ="):src.index("const OpSize* sz")]
     rows = {int(a): (int(b), int(c)) for a, b, c in re.findall(r"\{(\d+),\s*(\d+),\s*(\d+)\}", table)}
     for op in tv.OPS:
         assert rows[op.code] == (56 * op.n_in, 56 * op.n_out), op.name
-    assert sorted(c for c in rows if c >= 32) == [op.code for op in tv.OPS]
+    from tests import curve_vectors as cv  # the raw-limb ops are the tower's and the point formulas', nothing else
+
+    for op in cv.OPS:
+        assert rows[op.code] == (56 * op.n_in, 56 * op.n_out), op.name
+    assert [c for c in sorted(rows) if 32 <= c <= 68] == [op.code for op in tv.OPS]
+    assert sorted(c for c in rows if c >= 32) == [op.code for op in tv.OPS] + [op.code for op in cv.OPS]
