@@ -593,6 +593,29 @@ const char* blsgpu_code_name(int code);
  *        101 g2_psi 102 g2_psi2 103 jac_mul_zabs_ld [J -> J: 3->3] 104 jac_mul_zabs_lda [A -> J: 2->3] (the loaders
  *        read the element's input words at every call) 105 g2_on_curve 106 g2_in_subgroup 107 g2_in_subgroup_ld
  *        [A: 2->0], status = the answer
+ *     108..157 the multi-lane engines on raw limbs (csrc/coop_debug.hpp; the same 56-byte Fp values and stride rule),
+ *        each in the launch shape its production kernels use, [k -> m] in Fp values; Fp12 in tower order:
+ *        108 lacc_fin (pos, neg limb sums) [2->1], one element per lane
+ *        lane pairs (fp2x.hpp, gtx.hpp): one element per pair of a 128-lane block, lane k loads and stores coefficient k
+ *        109 fp2x_mul [4->2] 110 fp2x_sqr 111 fp2x_mul_xi [2->2] 112 fp2x_norm [2->2: the norm from either lane]
+ *        113 F_is_zero [2->0] 114 lc_xi<1>(d; t) [4->2] 115 lc_xi<1>(d; a, -b, -c) [8->2] 116 lc_xi<-1>(d; a, -b)
+ *        117 lc_xi<1>(d; a, -b) 118 lc_xi<3>(d; 4a, -5b) [6->2] 119 fp6x_mul [12->6] 120 fp12x_sqr [12->12]
+ *        121 fp12x_mul_by_014 (f, l0, l1, l4) [18->12] 122 miller_dbl_line (R) [6->12: R, l0, c1, c4]
+ *        123 miller_add_line (R, Q affine) [10->12] 124 jac_dbl [6->6] 125 jac_add [12->6] 126 jac_add_aff [10->6]
+ *        127 jac_neg [6->6] 128 jac_is_inf [6->0] 129 g2_psi 130 g2_psi2 131 jac_mul_zabs [6->6]; a predicate's status
+ *        = lane 0's answer | lane 1's << 1 (0 or 3)
+ *        six-lane groups (gt6.hpp): ten elements per 64-lane block, lane k loads and stores w-coefficient k
+ *        132 g6_mul [24->12] 133 g6_sqr 134 g6_cyc_sqr 135 g6_frob 1 136 g6_frob 2 137 g6_conj [12->12]
+ *        138 g6_line_mul (f, line record l0 c1 c4, xP, yP) [20->12] 139 g6_is_one [12->0], status = the answer
+ *        140 g6_pow_z 141 g6_final_exp [12->12]
+ *        16-lane groups (g2_coop.hpp): four elements per 64-lane block; element = a flag slot (word 0: the group is
+ *        live), the point J, the addend J; an element flagged off fills its group's LDS area with its input words,
+ *        runs every phase and writes nothing (out and status stay zero)
+ *        142 g2c_dbl 143 g2c_add 144 g2c_mul_zabs [13->6]
+ *        workgroup GT engine (gt_wave.hpp): one element per 128-lane block, operands in LDS in the w-basis
+ *        145 gtw_mul C distinct 146 C = A 147 C = B [24->12] 148 A = B = C [12->12] 149 gtw_mul<SPARSE> (f, l0, l1, l4)
+ *        [18->12] 150 gtw_cyc_sqr D = A 151 D distinct 152 gtw_conj 153 gtw_frob 1 154 gtw_frob 2 155 gtw_pow_z
+ *        156 gtw_final_exp [12->12] 157 gtw_miller_loop (P affine, Q affine; 192 lanes) [6->12]
  * Strides below an op's element size, and unknown ops, are refused with BLSGPU_ERR_ARGS.
  * Returns BLSGPU_OK or an error. */
 int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint32_t in_stride,

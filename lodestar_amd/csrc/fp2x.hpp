@@ -44,7 +44,10 @@ BLS_HD fp fp_swap(const fp& x) {
 
 // Redc(x1 y1 + x2 y2): product scanning of both products into one accumulator, one reduction.  Operands: limbs of x1,
 // x2, y1 < 2^29 and of y2 < 2^30 (the 16p - b1 offset form); column bound 14 (2^58 + 2^59) + 14 * 2^56 + 2^36 < 2^64
-// (fp2_mul_sb_body's c0).  Output: normalized limbs, value < 1.1 p for operand values < 8p (y2 < 16p + 8p).
+// (fp2_mul_sb_body's c0).  Output: normalized limbs, value < 1.1 p for operand values <= 8p, 8p itself included
+// (y2 <= 16p): out < p + (x1 y1 + x2 y2) / 2^392 <= p + (64 + 128) p^2 / 2^392 < 1.08 p, with p / 2^392 < 0.0004.  The
+// column bound depends on the limbs only, not on the values (tests/coop_vectors.py fp2x_mul: 8p - 1 per coefficient,
+// and 8p as gtx.hpp's F_add_nr of two 4p sums reaches it).
 BLS_INL fp fp_dot_body(const fp& x1, const fp& y1, const fp& x2, const fp& y2) {
   uint32_t m[BLS_NL];
   uint64_t acc = 0;
@@ -73,7 +76,8 @@ BLS_INL fp fp_dot_body(const fp& x1, const fp& y1, const fp& x2, const fp& y2) {
   return r;
 }
 
-// this lane's coefficient of a * b.  a, b: limbs < 2^29, values < 8p (normalized values or one fp_add_nr level)
+// this lane's coefficient of a * b.  a, b: limbs < 2^29, values <= 8p (normalized values or one fp_add_nr level);
+// result < 1.1 p (fp_dot_body)
 BLS_INL fp fp2x_mul_body(const fp& a, const fp& b) {
   const bool odd = fp2x_k() != 0;
   fp pa, b0, y;
@@ -86,7 +90,9 @@ BLS_INL fp fp2x_mul_body(const fp& a, const fp& b) {
   }
   return fp_dot_body(a, b0, pa, y);
 }
-// this lane's coefficient of a^2.  a: normalized limbs, value <= 4p (tower.hpp fp2_sqr_body's contract)
+// this lane's coefficient of a^2.  a: normalized limbs, value <= 4p (tower.hpp fp2_sqr_body's contract).  Result
+// < 1.04 p: one Montgomery product, out < p + x y / 2^392 with x y <= 8p * 12p on lane 0 ((a0 + a1)(a0 + 8p - a1)) and
+// 8p * 4p on lane 1, and 96 p / 2^392 < 0.039
 BLS_INL fp fp2x_sqr_body(const fp& a) {
   const bool odd = fp2x_k() != 0;
   fp x, y;

@@ -13,6 +13,10 @@
 //   R2 (2 lanes)  Y3 = E W - 8C
 // (D = 2(T - A - C)), so a doubling costs three product latencies and two recombinations, ~3x less than the serial
 // form.  The additions of a chain (five per [|z|]) run on the group's lane 0 with the register code of curve.hpp.
+// Operands: stored values (normalized, <= 2p), any representative, Z = 0 (mod p) for infinity.  Every coordinate that
+// g2c_dbl / g2c_add / g2c_mul_zabs leave in G2C_R is a lacc_fin result (<= 2p) or, on the exceptional path, jac_add's.
+// The recombinations stay inside lacc_fin's 15 terms per side (the largest: W = 6T - 6A - 6C - F, 13 on the negative
+// side; tests/test_coop_contracts.py audits it).
 // The phases are plain functions of (group LDS, lane in group) so the host build (tests/native/emu.cpp) runs them
 // lane by lane; g2c_sync() separates them on the device.
 #pragma once

@@ -7,6 +7,9 @@
 //   g6_cyc_sqr:  Granger-Scott squaring in the cyclotomic subgroup: lane k squares its output's Fp4 pair (3 Fp2
 //                squarings, each pair's shared by two lanes), then 3 X -+ 2 f_k;
 //   g6_frob, g6_conj, and the final exponentiation's one Fp6 inverse on the group's lane 0 (fp6_inv).
+// Operands: stored values (normalized, <= 2p).  Outputs, per Fp component: g6_mul, g6_sqr, g6_line_mul, g6_cyc_sqr and
+// g6_final_exp end on one fp_lc (g6_acc): < 1.003 p; g6_frob on an fp2_mul: < 1.1 p; g6_conj and g6_pow_z on an
+// fp2_neg or a pass-through: <= 2p.  (tests/coop_vectors.py checks these on the device, ops 132..141.)
 // The chain is pairing.hpp's final_exponentiation operation for operation (returns e^3 like it and gt_wave.hpp's), the
 // oracle-pinned sequence; the check kernel (k_group.hip k_group_check6) is compared job for job against the oracle.
 #pragma once

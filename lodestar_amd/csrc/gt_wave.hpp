@@ -12,6 +12,11 @@
 //     products, accumulated unreduced (lacc) and reduced once;
 //   * serial leftovers (two inversions, five Miller addition steps) run on lane 0 with the register code
 //     of tower.hpp / pairing.hpp.
+// Operands in LDS: stored values (normalized, <= 2p).  Every output component is a lacc_fin result, an fp_add / fp_sub
+// / fp_neg or a copy: normalized, <= 2p.  The recombinations hand lacc_fin at most 12 terms per side, inside its 15:
+// gtw_mul_rec six pair products, two terms per side each (measured: tests/test_coop_contracts.py audits lacc_fin's sums
+// under gtw_mul and the Miller schedule on the host); gtw_cyc_sqr 11, counted by hand from its sign table (device-only
+// code, which the host audit cannot run).
 // Same algorithm (operation for operation) as pairing.hpp's miller_loop / final_exponentiation, which the
 // oracle pins; tests/test_gpu_pipeline.py compares both against oracle/bls12_381.py.
 #pragma once

@@ -45,7 +45,9 @@ BLS_FN fp6x fp6x_mul(const fp6x& a, const fp6x& b) {
   return r;
 }
 
-// (a0 + a1 w)^2 = (s - t - v t) + 2 t w with t = a0 a1, s = (a0 + a1)(a0 + v a1); v t = (xi t2, t0, t1)
+// (a0 + a1 w)^2 = (s - t - v t) + 2 t w with t = a0 a1, s = (a0 + a1)(a0 + v a1); v t = (xi t2, t0, t1).  a: stored
+// values, <= 2p (not fp6x_mul's 4p: the sums a0 + a1 are fp6x_mul operands).  Every output coefficient is one fp_lc:
+// < 1.003 p, as fp6x_mul's and fp12x_mul_by_014's (operands: stored values)
 BLS_FN fp12x fp12x_sqr(const fp12x& a) {
   const fp6x t = fp6x_mul(a.c0, a.c1);
   fp6x u, w;

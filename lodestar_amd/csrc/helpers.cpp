@@ -932,6 +932,20 @@ int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint
   const OpSize* sz = nullptr;
   for (const OpSize& o : kOpSizes)
     if (o.op == op) sz = &o;
+  // the multi-lane engines' hooks (coop_debug.hpp): lacc_fin 108, lane pairs 109..131, six-lane groups 132..141, g2c
+  // groups 142..144 (a flag slot, the point, the addend), the workgroup GT engine 145..157
+  static const OpSize kCoopSizes[] = {
+      {108, 112, 56}, {109, 224, 112}, {110, 112, 112}, {111, 112, 112}, {112, 112, 112}, {113, 112, 0},
+      {114, 224, 112}, {115, 448, 112}, {116, 336, 112}, {117, 336, 112}, {118, 336, 112}, {119, 672, 336},
+      {120, 672, 672}, {121, 1008, 672}, {122, 336, 672}, {123, 560, 672}, {124, 336, 336}, {125, 672, 336},
+      {126, 560, 336}, {127, 336, 336}, {128, 336, 0}, {129, 336, 336}, {130, 336, 336}, {131, 336, 336},
+      {132, 1344, 672}, {133, 672, 672}, {134, 672, 672}, {135, 672, 672}, {136, 672, 672}, {137, 672, 672},
+      {138, 1120, 672}, {139, 672, 0}, {140, 672, 672}, {141, 672, 672}, {142, 728, 336}, {143, 728, 336},
+      {144, 728, 336}, {145, 1344, 672}, {146, 1344, 672}, {147, 1344, 672}, {148, 672, 672}, {149, 1008, 672},
+      {150, 672, 672}, {151, 672, 672}, {152, 672, 672}, {153, 672, 672}, {154, 672, 672}, {155, 672, 672},
+      {156, 672, 672}, {157, 336, 672}};
+  for (const OpSize& o : kCoopSizes)
+    if (o.op == op) sz = &o;
   if (!sz || in_stride < sz->in || out_stride < sz->out) return BLSGPU_ERR_ARGS;
   const bool tower = op >= 32;  // limb words are read and written as uint32: word-aligned elements only
   if (tower && (in_stride % 4 || out_stride % 4 || out_stride == 0)) return BLSGPU_ERR_ARGS;
@@ -948,7 +962,10 @@ int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint
     HIPCHK(hipMalloc(&dst.p, (size_t)n * 4));
     HIPCHK(hipMemcpyAsync(din.p, in, (size_t)n * in_stride, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(dout.p, 0, (size_t)n * out_stride, s));
-    if (op >= 69)  // (curve_debug.hpp CRV_OP_FIRST)
+    if (op >= 108) {  // (coop_debug.hpp COOP_OP_FIRST)
+      HIPCHK(hipMemsetAsync(dst.p, 0, (size_t)n * 4, s));
+      launch_debug_coop(op, n, (uint8_t*)din.p, in_stride, (uint8_t*)dout.p, out_stride, (int32_t*)dst.p, s);
+    } else if (op >= 69)  // (curve_debug.hpp CRV_OP_FIRST)
       launch_debug_curve(op, n, (uint8_t*)din.p, in_stride, (uint8_t*)dout.p, out_stride, (int32_t*)dst.p, s);
     else if (tower)
       launch_debug_tower(op, n, (uint8_t*)din.p, in_stride, (uint8_t*)dout.p, out_stride, (int32_t*)dst.p, s);

@@ -387,3 +387,8 @@ void launch_debug_tower(int op, uint32_t n, const uint8_t* in, uint32_t in_strid
 // the point formulas' raw-limb hooks (ops 69..107, curve_debug.hpp): the same launch shape and stride rule
 void launch_debug_curve(int op, uint32_t n, const uint8_t* in, uint32_t in_stride, uint8_t* out, uint32_t out_stride,
                         int32_t* status, hipStream_t s);
+// the multi-lane engines' raw-limb hooks (ops 108..157, coop_debug.hpp): each engine in its production launch shape
+// (an element per lane pair, per six lanes, per 16-lane group, per block); the same stride rule; `status` zeroed by
+// the caller (a g2c element flagged off writes nothing)
+void launch_debug_coop(int op, uint32_t n, const uint8_t* in, uint32_t in_stride, uint8_t* out, uint32_t out_stride,
+                       int32_t* status, hipStream_t s);

@@ -29,8 +29,27 @@ BLS_INL uint32_t fp_p32_limb(int i) {
   if (i == BLS_NL - 1) lo = FP_P.l[i] << 5;
   return lo | (i ? (FP_P.l[i - 1] >> (BLS_LB - 5)) : 0u);
 }
+#if defined(BLS_LACC_AUDIT)
+// Host test builds only (tests/native/emu.cpp): the largest positive-side and negative-side sums lacc_fin has been
+// handed, in units of p.  No caller counts its own terms; lacc_fin needs pos < 32p (v = pos + 32p - neg < 64p, the
+// quotient estimate's range) and neg <= 32p (v >= 0), which "at most 15 terms per side" of values <= 2p keeps.
+static double lacc_audit_max[2];
+static inline void lacc_audit(const lacc& a) {
+  long double p = 0, s[2] = {0, 0}, sc = 1;
+  for (int i = 0; i < BLS_NL; i++, sc *= (long double)(1u << BLS_LB)) {
+    p += sc * FP_P.l[i];
+    s[0] += sc * a.pos[i];
+    s[1] += sc * a.neg[i];
+  }
+  for (int k = 0; k < 2; k++)
+    if ((double)(s[k] / p) > lacc_audit_max[k]) lacc_audit_max[k] = (double)(s[k] / p);
+}
+#endif
 // pos - neg (mod p), result <= 2p normalized
 BLS_INL fp lacc_fin(const lacc& a) {
+#if defined(BLS_LACC_AUDIT)
+  lacc_audit(a);
+#endif
   uint32_t v[BLS_NL];
   int64_t c = 0;
 #pragma unroll

@@ -2,6 +2,7 @@
 // so tests can check the exact kernel arithmetic against the oracle without a GPU.  It is never linked
 // into libblsgpu.so (the product has no CPU path).  Byte formats: canonical big-endian 48-byte Fp.
 #include <string.h>
+#define BLS_LACC_AUDIT 1  // lacc_fin records the largest sums it is handed (lacc.hpp; this build only)
 #include "../../lodestar_amd/csrc/ops.hpp"
 #include "../../lodestar_amd/csrc/msm.hpp"
 #include "../../lodestar_amd/csrc/lacc.hpp"
@@ -9,6 +10,7 @@
 #include "../../lodestar_amd/csrc/gt_wave.hpp"
 #include "../../lodestar_amd/csrc/tower_debug.hpp"
 #include "../../lodestar_amd/csrc/curve_debug.hpp"
+#include "../../lodestar_amd/csrc/coop_debug.hpp"
 
 #if defined(BLS_COUNT_OPS)
 unsigned long long bls_count_mul = 0, bls_count_sqr = 0, bls_count_half = 0;
@@ -518,3 +520,9 @@ extern "C" void emu_fp2_mul_sb_limbs(const uint32_t* in56, uint32_t* out28) {
 extern "C" int emu_tower_op(int op, const uint32_t* in, uint32_t* out) { return tower_debug_op(op, in, out); }
 // The point formulas' hooks (curve_debug.hpp, ops 69..107; tests/test_curve_contracts.py, tests/curve_vectors.py).
 extern "C" int emu_curve_op(int op, const uint32_t* in, uint32_t* out) { return curve_debug_op(op, in, out); }
+// The multi-lane engines' hooks, the host-compilable subset run lane by lane (coop_debug.hpp coop_host_op: lacc_fin,
+// the g2c phases, gtw_mul_prod / gtw_mul_rec, the Miller schedule; tests/test_coop_contracts.py, tests/coop_vectors.py).
+extern "C" int emu_coop_op(int op, const uint32_t* in, uint32_t* out) { return coop_host_op(op, in, out); }
+// lacc_fin's audit (lacc.hpp BLS_LACC_AUDIT): the largest positive / negative side seen since the last reset, in p
+extern "C" void emu_lacc_audit_reset() { lacc_audit_max[0] = lacc_audit_max[1] = 0; }
+extern "C" double emu_lacc_audit_max(int side) { return lacc_audit_max[side ? 1 : 0]; }
