@@ -616,6 +616,9 @@ const char* blsgpu_code_name(int code);
  *        145 gtw_mul C distinct 146 C = A 147 C = B [24->12] 148 A = B = C [12->12] 149 gtw_mul<SPARSE> (f, l0, l1, l4)
  *        [18->12] 150 gtw_cyc_sqr D = A 151 D distinct 152 gtw_conj 153 gtw_frob 1 154 gtw_frob 2 155 gtw_pow_z
  *        156 gtw_final_exp [12->12] 157 gtw_miller_loop (P affine, Q affine; 192 lanes) [6->12]
+ *     160..162 lane pairs again, the hot loop of the [|z|] chains (158 and 159 are unassigned):
+ *        160 jac_dbl n times (J, then a slot whose word 0 is n <= 64, the same over a launch) [7->6]
+ *        161 jac_mul_zabs_ld [J -> J: 6->6] 162 jac_mul_zabs_lda [A -> J: 4->6]
  * Strides below an op's element size, and unknown ops, are refused with BLSGPU_ERR_ARGS.
  * Returns BLSGPU_OK or an error. */
 int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint32_t in_stride,

@@ -96,16 +96,28 @@ def up_to_date():
     return all(os.path.getmtime(d) <= t for d in _deps())
 
 
-def build(force=False, verbose=True):
-    if not force and up_to_date():
-        build_node_addon(verbose=verbose)
-        return LIB
-    objs = []
+def common_flags():
+    """(flags every TU is compiled with, the BLSGPU_DEFINES in them, the BLSGPU_CFLAGS in them)"""
     common = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", os.path.join(ROOT, "include")]
     defines = os.environ.get("BLSGPU_DEFINES", "").split()  # e.g. BLSGPU_WPE=2
     common += ["-D" + d for d in defines]
     cflags = os.environ.get("BLSGPU_CFLAGS", "").split()  # tuning variants: extra compiler flags
     common += cflags
+    return common, defines, cflags
+
+
+def tu_compile_flags(src):
+    """Everything between the compiler and `-c SRC -o OBJ` for one translation unit of the product build
+    (tools/inst_count.py compiles to assembly with exactly these)."""
+    return common_flags()[0] + ["-D" + d for d in tu_defines().get(src, [])] + tu_cflags().get(src, [])
+
+
+def build(force=False, verbose=True):
+    if not force and up_to_date():
+        build_node_addon(verbose=verbose)
+        return LIB
+    objs = []
+    common, defines, cflags = common_flags()
     tu_defs = tu_defines()
     os.makedirs(OBJ_DIR, exist_ok=True)
     # objects are keyed by the library name and the defines, so variant builds never reuse each other's objects
@@ -124,7 +136,7 @@ def build(force=False, verbose=True):
         objs.append(obj)
         if not force and os.path.exists(obj) and all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in _tu_deps(src)):
             continue
-        cmd = [HIPCC] + common + ["-D" + d for d in tdefs] + tflags + ["-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [HIPCC] + tu_compile_flags(src) + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd)))

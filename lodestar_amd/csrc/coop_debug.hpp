@@ -5,7 +5,7 @@
 // every engine runs in the shape its production kernels use (k_coop_debug.hip), an element per lane PAIR, per group of
 // SIX lanes, per group of 16 lanes (four per block) or per 128 / 192-lane block, so the cross-lane exchanges, the
 // lane-dependent select tables, the pair-combined branch conditions, the LDS slots other lanes wrote and the barrier
-// schedules are what is tested (blsgpu_debug_op ops 108..157; records: tests/coop_vectors.py).
+// schedules are what is tested (blsgpu_debug_op ops 108..157 and 160..162; records: tests/coop_vectors.py).
 // The host build (tests/native/emu.cpp emu_coop_op) runs the host-compilable subset lane by lane: lacc_fin, the g2c
 // phases, gtw_mul_prod / gtw_mul_rec and the Miller schedule.  The lane-pair and six-lane ops are device-only.
 //
@@ -26,6 +26,9 @@
 #define COOP_OP_GTW 145       // 145..157: one element per block
 #define COOP_OP_GTW_MILLER 157
 #define COOP_OP_LAST 157
+// lane pairs again, for the chains' hot loop (158 and 159 stay unassigned: refused like every unknown op)
+#define COOP_OP_PAIR2 160       // 160: jac_dbl n times (in: x, y, z, then a slot whose word 0 is n <= 64; uniform over a launch)
+#define COOP_OP_PAIR2_LAST 162  // 161 / 162: the [|z|] chain, jac_mul_zabs_ld (Jacobian in) / jac_mul_zabs_lda (affine in)
 #define COOP_G2C_IN_FPS 13    // Fp slots of a g2c element
 
 BLS_INL fp coop_lacc_fin(const uint32_t* w) {
@@ -237,6 +240,24 @@ BLS_INL int coop_pair_op(int op, const uint32_t* w, uint32_t* o) {
     case 129: px_stj(o, g2_psi(px_ldj(w, 0))); break;
     case 130: px_stj(o, g2_psi2(px_ldj(w, 0))); break;
     case 131: px_stj(o, jac_mul_zabs(px_ldj(w, 0))); break;
+    case 160: {
+      g2jx r = px_ldj(w, 0);
+      const uint32_t n = w[6 * BLS_NL] < 64u ? w[6 * BLS_NL] : 64u;
+#pragma unroll 1
+      for (uint32_t i = 0; i < n; i++) r = jac_dbl(r);
+      px_stj(o, r);
+      break;
+    }
+    // the loaders read the record's input words at every call, as the kernels' loaders read their SoA buffers
+    case 161: px_stj(o, jac_mul_zabs_ld<fp2x>([&]() { return px_ldj(w, 0); })); break;
+    case 162:
+      px_stj(o, jac_mul_zabs_lda<fp2x>([&]() {
+               aff<fp2x> Q;
+               Q.x = px_ld(w, 0);
+               Q.y = px_ld(w, 1);
+               return Q;
+             }));
+      break;
     default: st = -2;
   }
   return st;

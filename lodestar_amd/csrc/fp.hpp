@@ -5,7 +5,8 @@
 // issues at half rate, and so do the carry-flag adds (v_add_co/v_addc_co) -- but a 28-bit limb product
 // is < 2^56, so every Montgomery column (up to 28 products) is summed by plain v_mad_u64_u32 with NO
 // carry flags at all.  One Montgomery multiplication = 392 v_mad_u64_u32 (14^2 a*b + 14^2 m*p),
-// one squaring = 301.
+// one squaring = 301.  Each column is one MAD chain that starts from the carried, shifted accumulator (BLS_MAC below):
+// 87 instructions around the 392 MADs of fp_mul_r (profiles/inst_counts.json).
 //
 // Value invariant for every stored element: 0 <= value <= 2p, limbs normalized (< 2^28, top limb holds
 // the rest).  fp_mul/fp_sqr outputs are < p + 2^-6 p.  Operands of fp_mul may be un-normalized sums
@@ -76,6 +77,29 @@ extern unsigned long long bls_count_mul, bls_count_sqr, bls_count_half;
 // ------------------------------------------------------------------------------------------------
 // Montgomery multiplication: finely integrated product scanning (column-wise a*b and m*p).
 // ------------------------------------------------------------------------------------------------
+// One column = ONE chain of v_mad_u64_u32, the first taking the carried, shifted accumulator as its addend.  Left
+// alone, LLVM reassociates a column's sum so that the carried accumulator (the operand computed last) is added last:
+// the products are summed from zero in a second register pair and merged by a 64-bit add per column.  Dependent MADs
+// issue as fast as independent ones here (profiles/r02_mad_chain.json), so the split hides nothing and the add is one
+// more issue slot per column (26 per reduction).  BLS_MAC pins the order in plain C++: the reassociation only walks
+// through partial sums that have a single use, so each partial sum gets a second, free one -- an assumption (true by
+// the column bounds below 2^64 of every body that uses it) that is dropped before instruction selection.  Every
+// `acc + x * y` is then matched on its own.  (An empty or real inline-asm step on the accumulator pins the order too,
+// but gfx950's hazard recognizer puts an s_nop between an asm's result and the VALU instruction that reads it.)
+// The host build has no use for it: the same integers either way, limb for limb.
+// This leans on how LLVM's reassociation pass treats multi-use values, which no compiler release promises: after a
+// ROCm upgrade regenerate profiles/inst_counts.json (tools/inst_count.py) and check that the product routines still
+// hold no per-column 64-bit add.  BLS_NO_MAC_CHAIN=1 (BLSGPU_DEFINES / BLSGPU_TU_DEFINES of build.py) builds the plain
+// sums again, for comparison.
+#if defined(__HIP_DEVICE_COMPILE__) && !BLS_NO_MAC_CHAIN
+#define BLS_MAC(acc, x, y)                  \
+  do {                                      \
+    (acc) += (uint64_t)(x) * (uint64_t)(y); \
+    __builtin_assume((acc) != ~0ull);       \
+  } while (0)
+#else
+#define BLS_MAC(acc, x, y) ((acc) += (uint64_t)(x) * (uint64_t)(y))
+#endif
 BLS_INL fp fp_mul_body(const fp& a, const fp& b) {
   fp r;
   uint32_t m[BLS_NL];
@@ -83,20 +107,20 @@ BLS_INL fp fp_mul_body(const fp& a, const fp& b) {
 #pragma unroll
   for (int k = 0; k < BLS_NL; k++) {
 #pragma unroll
-    for (int i = 0; i <= k; i++) acc += (uint64_t)a.l[i] * b.l[k - i];
+    for (int i = 0; i <= k; i++) BLS_MAC(acc, a.l[i], b.l[k - i]);
 #pragma unroll
-    for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * FP_P.l[k - i];
+    for (int i = 0; i < k; i++) BLS_MAC(acc, m[i], FP_P.l[k - i]);
     uint32_t mk = ((uint32_t)acc * BLS_N0INV) & BLS_MASK;
     m[k] = mk;
-    acc += (uint64_t)mk * FP_P.l[0];
+    BLS_MAC(acc, mk, FP_P.l[0]);
     acc >>= BLS_LB;
   }
 #pragma unroll
   for (int k = BLS_NL; k < 2 * BLS_NL - 1; k++) {
 #pragma unroll
     for (int i = k - BLS_NL + 1; i < BLS_NL; i++) {
-      acc += (uint64_t)a.l[i] * b.l[k - i];
-      acc += (uint64_t)m[i] * FP_P.l[k - i];
+      BLS_MAC(acc, a.l[i], b.l[k - i]);
+      BLS_MAC(acc, m[i], FP_P.l[k - i]);
     }
     r.l[k - BLS_NL] = (uint32_t)acc & BLS_MASK;
     acc >>= BLS_LB;
@@ -115,22 +139,22 @@ BLS_INL fp fp_sqr_body(const fp& a) {
 #pragma unroll
   for (int k = 0; k < BLS_NL; k++) {
 #pragma unroll
-    for (int i = 0; 2 * i < k; i++) acc += (uint64_t)a2[i] * a.l[k - i];
-    if ((k & 1) == 0) acc += (uint64_t)a.l[k >> 1] * a.l[k >> 1];
+    for (int i = 0; 2 * i < k; i++) BLS_MAC(acc, a2[i], a.l[k - i]);
+    if ((k & 1) == 0) BLS_MAC(acc, a.l[k >> 1], a.l[k >> 1]);
 #pragma unroll
-    for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * FP_P.l[k - i];
+    for (int i = 0; i < k; i++) BLS_MAC(acc, m[i], FP_P.l[k - i]);
     uint32_t mk = ((uint32_t)acc * BLS_N0INV) & BLS_MASK;
     m[k] = mk;
-    acc += (uint64_t)mk * FP_P.l[0];
+    BLS_MAC(acc, mk, FP_P.l[0]);
     acc >>= BLS_LB;
   }
 #pragma unroll
   for (int k = BLS_NL; k < 2 * BLS_NL - 1; k++) {
 #pragma unroll
-    for (int i = k - BLS_NL + 1; 2 * i < k; i++) acc += (uint64_t)a2[i] * a.l[k - i];
-    if ((k & 1) == 0) acc += (uint64_t)a.l[k >> 1] * a.l[k >> 1];
+    for (int i = k - BLS_NL + 1; 2 * i < k; i++) BLS_MAC(acc, a2[i], a.l[k - i]);
+    if ((k & 1) == 0) BLS_MAC(acc, a.l[k >> 1], a.l[k >> 1]);
 #pragma unroll
-    for (int i = k - BLS_NL + 1; i < BLS_NL; i++) acc += (uint64_t)m[i] * FP_P.l[k - i];
+    for (int i = k - BLS_NL + 1; i < BLS_NL; i++) BLS_MAC(acc, m[i], FP_P.l[k - i]);
     r.l[k - BLS_NL] = (uint32_t)acc & BLS_MASK;
     acc >>= BLS_LB;
   }

@@ -946,6 +946,11 @@ int blsgpu_debug_op(blsgpu_ctx* ctx, int op, uint32_t n, const uint8_t* in, uint
       {156, 672, 672}, {157, 336, 672}};
   for (const OpSize& o : kCoopSizes)
     if (o.op == op) sz = &o;
+  // lane pairs again (coop_debug.hpp COOP_OP_PAIR2): n doublings (the point, then the count's slot), the [|z|] chain
+  // from a Jacobian / an affine point
+  static const OpSize kPair2Sizes[] = {{160, 392, 336}, {161, 336, 336}, {162, 224, 336}};
+  for (const OpSize& o : kPair2Sizes)
+    if (o.op == op) sz = &o;
   if (!sz || in_stride < sz->in || out_stride < sz->out) return BLSGPU_ERR_ARGS;
   const bool tower = op >= 32;  // limb words are read and written as uint32: word-aligned elements only
   if (tower && (in_stride % 4 || out_stride % 4 || out_stride == 0)) return BLSGPU_ERR_ARGS;

@@ -1,7 +1,7 @@
-// The multi-lane engines' raw-limb test hooks on the device (blsgpu_debug_op ops 108..157, coop_debug.hpp).  One kernel
+// The multi-lane engines' raw-limb test hooks on the device (blsgpu_debug_op ops 108..157 and 160..162, coop_debug.hpp).  One kernel
 // per engine, each in the launch shape its production kernels use -- that shape is what these hooks are for:
 //   k_coop_lane   op 108        128-lane blocks, one record per lane (lacc_fin)
-//   k_coop_pair   ops 109..131  128-lane blocks, one element per lane PAIR (k_miller, k_sig, k_msm); exit per pair
+//   k_coop_pair   ops 109..131, 160..162  128-lane blocks, one element per lane PAIR (k_miller, k_sig, k_msm); exit per pair
 //   k_coop_g6     ops 132..141  one wave, ten groups of six lanes, lanes 60-63 leave at once (k_group_check6)
 //   k_coop_g2c    ops 142..144  one wave, four 16-lane groups with their LDS areas (k_hash_clear_coop); a group whose
 //                               element is flagged off runs every phase on arbitrary words and writes nothing
@@ -107,7 +107,7 @@ void launch_debug_coop(int op, uint32_t n, const uint8_t* in, uint32_t in_stride
   if (op == COOP_OP_LACC)
     hipLaunchKernelGGL(k_coop_lane, dim3((n + COOP_LANES - 1) / COOP_LANES), dim3(COOP_LANES), 0, s, n, in, in_stride,
                        out, out_stride, status);
-  else if (op <= COOP_OP_PAIR_LAST)
+  else if (op <= COOP_OP_PAIR_LAST || (op >= COOP_OP_PAIR2 && op <= COOP_OP_PAIR2_LAST))
     hipLaunchKernelGGL(k_coop_pair, dim3((2 * n + COOP_LANES - 1) / COOP_LANES), dim3(COOP_LANES), 0, s, op, n, in,
                        in_stride, out, out_stride, status);
   else if (op <= COOP_OP_G6_LAST)

@@ -111,23 +111,23 @@ BLS_INL fp2 fp2_mul_sb_body(const fp& a0, const fp& a1, const fp& b0, const fp& 
     const int lo = k < BLS_NL ? 0 : k - BLS_NL + 1, hi = k < BLS_NL ? k : BLS_NL - 1;
 #pragma unroll
     for (int i = lo; i <= hi; i++) {
-      acc0 += (uint64_t)a0.l[i] * b0.l[k - i];
-      acc1 += (uint64_t)a0.l[i] * b1.l[k - i];
-      acc0 += (uint64_t)a1.l[i] * nb[k - i];
-      acc1 += (uint64_t)a1.l[i] * b0.l[k - i];
+      BLS_MAC(acc0, a0.l[i], b0.l[k - i]);
+      BLS_MAC(acc1, a0.l[i], b1.l[k - i]);
+      BLS_MAC(acc0, a1.l[i], nb[k - i]);
+      BLS_MAC(acc1, a1.l[i], b0.l[k - i]);
     }
     const int mhi = k < BLS_NL ? k - 1 : BLS_NL - 1;
 #pragma unroll
     for (int i = lo; i <= mhi; i++) {
-      acc0 += (uint64_t)m0[i] * FP_P.l[k - i];
-      acc1 += (uint64_t)m1[i] * FP_P.l[k - i];
+      BLS_MAC(acc0, m0[i], FP_P.l[k - i]);
+      BLS_MAC(acc1, m1[i], FP_P.l[k - i]);
     }
     if (k < BLS_NL) {
       const uint32_t q0 = ((uint32_t)acc0 * BLS_N0INV) & BLS_MASK, q1 = ((uint32_t)acc1 * BLS_N0INV) & BLS_MASK;
       m0[k] = q0;
       m1[k] = q1;
-      acc0 += (uint64_t)q0 * FP_P.l[0];
-      acc1 += (uint64_t)q1 * FP_P.l[0];
+      BLS_MAC(acc0, q0, FP_P.l[0]);
+      BLS_MAC(acc1, q1, FP_P.l[0]);
     } else {
       r.c0.l[k - BLS_NL] = (uint32_t)acc0 & BLS_MASK;
       r.c1.l[k - BLS_NL] = (uint32_t)acc1 & BLS_MASK;
@@ -151,10 +151,54 @@ BLS_INL fp2 fp2_mul_sb_body(const fp& a0, const fp& a1, const fp& b0, const fp& 
 // Fp2 squaring (complex method): c0 = (a0 + a1)(a0 - a1), c1 = 2 a0 a1 -- two independent products.  Input:
 // normalized limbs, values <= 4p (stored values, or fp2_add_norm of two); a0 - a1 goes to the product as
 // a0 + 8p - a1 (fp_sub_k8, no reduction), so an input above 2p never underflows.  Outputs < 1.05 p.
+#if defined(__HIP_DEVICE_COMPILE__)
+// (Redc(x0 y0), Redc(x1 y1)): fp_mul_body twice, written column by column over two accumulators so the two chains
+// of fp2_sqr_r stay interleaved and each result ends in the registers it is returned in (two fp_mul_body in a row
+// cost 14 v_mov there; fp2_mul_fp_r, whose products share an operand, is as short with two and needs fewer VGPRs).
+// It holds both operand sets and both m arrays at once: fp2_sqr_r takes 132 VGPRs where it took 114.
+// Operands and outputs as fp_mul_body; the same integers, limb for limb.
+BLS_INL fp2 fp_mul_pair_body(const fp& x0, const fp& y0, const fp& x1, const fp& y1) {
+  uint32_t m0[BLS_NL], m1[BLS_NL];
+  uint64_t acc0 = 0, acc1 = 0;
+  fp2 r;
+#pragma unroll
+  for (int k = 0; k < 2 * BLS_NL - 1; k++) {
+    const int lo = k < BLS_NL ? 0 : k - BLS_NL + 1, hi = k < BLS_NL ? k : BLS_NL - 1;
+#pragma unroll
+    for (int i = lo; i <= hi; i++) {
+      BLS_MAC(acc0, x0.l[i], y0.l[k - i]);
+      BLS_MAC(acc1, x1.l[i], y1.l[k - i]);
+    }
+    const int mhi = k < BLS_NL ? k - 1 : BLS_NL - 1;
+#pragma unroll
+    for (int i = lo; i <= mhi; i++) {
+      BLS_MAC(acc0, m0[i], FP_P.l[k - i]);
+      BLS_MAC(acc1, m1[i], FP_P.l[k - i]);
+    }
+    if (k < BLS_NL) {
+      const uint32_t q0 = ((uint32_t)acc0 * BLS_N0INV) & BLS_MASK, q1 = ((uint32_t)acc1 * BLS_N0INV) & BLS_MASK;
+      m0[k] = q0;
+      m1[k] = q1;
+      BLS_MAC(acc0, q0, FP_P.l[0]);
+      BLS_MAC(acc1, q1, FP_P.l[0]);
+    } else {
+      r.c0.l[k - BLS_NL] = (uint32_t)acc0 & BLS_MASK;
+      r.c1.l[k - BLS_NL] = (uint32_t)acc1 & BLS_MASK;
+    }
+    acc0 >>= BLS_LB;
+    acc1 >>= BLS_LB;
+  }
+  r.c0.l[BLS_NL - 1] = (uint32_t)acc0;
+  r.c1.l[BLS_NL - 1] = (uint32_t)acc1;
+  return r;
+}
+#else
+BLS_INL fp2 fp_mul_pair_body(const fp& x0, const fp& y0, const fp& x1, const fp& y1) {
+  return fp2_make(fp_mul_body(x0, y0), fp_mul_body(x1, y1));
+}
+#endif
 BLS_INL fp2 fp2_sqr_body(const fp2& a) {
-  const fp c0 = fp_mul_body(fp_add_nr(a.c0, a.c1), fp_sub_k8(a.c0, a.c1));
-  const fp c1 = fp_mul_body(fp_add_nr(a.c0, a.c0), a.c1);
-  return fp2_make(c0, c1);
+  return fp_mul_pair_body(fp_add_nr(a.c0, a.c1), fp_sub_k8(a.c0, a.c1), fp_add_nr(a.c0, a.c0), a.c1);
 }
 
 // Device call boundary of the Fp2 products (fp.hpp "call-granularity policy"):
