@@ -6,7 +6,8 @@
 // is < 2^56, so every Montgomery column (up to 28 products) is summed by plain v_mad_u64_u32 with NO
 // carry flags at all.  One Montgomery multiplication = 392 v_mad_u64_u32 (14^2 a*b + 14^2 m*p),
 // one squaring = 301.  Each column is one MAD chain that starts from the carried, shifted accumulator (BLS_MAC below):
-// 87 instructions around the 392 MADs of fp_mul_r (profiles/inst_counts.json).
+// 87 instructions around the 392 MADs of fp_mul_r (profiles/inst_counts.json).  The loop is written once (mont_scan
+// below); every product body, here and in fp2x.hpp / tower.hpp, is an instance of it.
 //
 // Value invariant for every stored element: 0 <= value <= 2p, limbs normalized (< 2^28, top limb holds
 // the rest).  fp_mul/fp_sqr outputs are < p + 2^-6 p.  Operands of fp_mul may be un-normalized sums
@@ -89,8 +90,9 @@ extern unsigned long long bls_count_mul, bls_count_sqr, bls_count_half;
 // The host build has no use for it: the same integers either way, limb for limb.
 // This leans on how LLVM's reassociation pass treats multi-use values, which no compiler release promises: after a
 // ROCm upgrade regenerate profiles/inst_counts.json (tools/inst_count.py) and check that the product routines still
-// hold no per-column 64-bit add.  BLS_NO_MAC_CHAIN=1 (BLSGPU_DEFINES / BLSGPU_TU_DEFINES of build.py) builds the plain
-// sums again, for comparison.
+// hold no per-column 64-bit add.  They all run the one loop below (mont_scan), so the routines keep or lose the
+// property together.  BLS_NO_MAC_CHAIN=1 (BLSGPU_DEFINES / BLSGPU_TU_DEFINES of build.py) builds the plain sums again,
+// for comparison.
 #if defined(__HIP_DEVICE_COMPILE__) && !BLS_NO_MAC_CHAIN
 #define BLS_MAC(acc, x, y)                  \
   do {                                      \
@@ -100,74 +102,72 @@ extern unsigned long long bls_count_mul, bls_count_sqr, bls_count_half;
 #else
 #define BLS_MAC(acc, x, y) ((acc) += (uint64_t)(x) * (uint64_t)(y))
 #endif
-BLS_INL fp fp_mul_body(const fp& a, const fp& b) {
-  fp r;
-  uint32_t m[BLS_NL];
-  uint64_t acc = 0;
+// The one Montgomery loop: NA reductions side by side, product scanning.  ab(acc, i, j) adds the operand products of
+// limb pair (i, j) to the NA accumulators, with BLS_MAC only; everything else -- the column bounds, the m p terms, the
+// quotient digits, the limb emission -- is here and nowhere else.  Every product body (fp_mul_body, fp_sqr_body,
+// fp2x.hpp fp_dot_body, tower.hpp fp2_mul_sb_body and fp_mul_pair_body) is its operand preparation and one call, the
+// same code on the device and in the host build.
+// Required of the caller: every column sum stays below 2^64 - 1 (the assumption in BLS_MAC rests on it).  A column is
+// the carried accumulator (< 2^36), the caller's up to 14 limb pairs and up to 14 terms m p < 2^56; each body states
+// its operand bounds and the arithmetic that meets this.  Output: normalized limbs (the top limb holds the rest),
+// value < p + (the integer the column sums add up to) / 2^392.
+#define BLS_AB_INL __attribute__((always_inline))  // on the lambda handed to mont_scan: part of the unrolled column
+template <int NA, class AB>
+BLS_INL void mont_scan(fp (&r)[NA], const AB& ab) {
+  uint32_t m[NA][BLS_NL];
+  uint64_t acc[NA] = {};
 #pragma unroll
-  for (int k = 0; k < BLS_NL; k++) {
+  for (int k = 0; k < 2 * BLS_NL - 1; k++) {
+    const int lo = k < BLS_NL ? 0 : k - BLS_NL + 1, hi = k < BLS_NL ? k : BLS_NL - 1;
 #pragma unroll
-    for (int i = 0; i <= k; i++) BLS_MAC(acc, a.l[i], b.l[k - i]);
+    for (int i = lo; i <= hi; i++) ab(acc, i, k - i);
+    const int mhi = k < BLS_NL ? k - 1 : BLS_NL - 1;
 #pragma unroll
-    for (int i = 0; i < k; i++) BLS_MAC(acc, m[i], FP_P.l[k - i]);
-    uint32_t mk = ((uint32_t)acc * BLS_N0INV) & BLS_MASK;
-    m[k] = mk;
-    BLS_MAC(acc, mk, FP_P.l[0]);
-    acc >>= BLS_LB;
-  }
+    for (int i = lo; i <= mhi; i++) {
 #pragma unroll
-  for (int k = BLS_NL; k < 2 * BLS_NL - 1; k++) {
-#pragma unroll
-    for (int i = k - BLS_NL + 1; i < BLS_NL; i++) {
-      BLS_MAC(acc, a.l[i], b.l[k - i]);
-      BLS_MAC(acc, m[i], FP_P.l[k - i]);
+      for (int j = 0; j < NA; j++) BLS_MAC(acc[j], m[j][i], FP_P.l[k - i]);
     }
-    r.l[k - BLS_NL] = (uint32_t)acc & BLS_MASK;
-    acc >>= BLS_LB;
+#pragma unroll
+    for (int j = 0; j < NA; j++) {
+      if (k < BLS_NL) {
+        const uint32_t q = ((uint32_t)acc[j] * BLS_N0INV) & BLS_MASK;
+        m[j][k] = q;
+        BLS_MAC(acc[j], q, FP_P.l[0]);
+      } else {
+        r[j].l[k - BLS_NL] = (uint32_t)acc[j] & BLS_MASK;
+      }
+      acc[j] >>= BLS_LB;
+    }
   }
-  r.l[BLS_NL - 1] = (uint32_t)acc;
-  return r;
+#pragma unroll
+  for (int j = 0; j < NA; j++) r[j].l[BLS_NL - 1] = (uint32_t)acc[j];
 }
 
+// Redc(a b).  Operands: limbs < 2^30 (header comment); column bound 14 * 2^60 + 14 * 2^56 + 2^36 < 2^64.
+BLS_INL fp fp_mul_body(const fp& a, const fp& b) {
+  fp r[1];
+  mont_scan<1>(r, [&](uint64_t* acc, int i, int j) BLS_AB_INL { BLS_MAC(acc[0], a.l[i], b.l[j]); });
+  return r[0];
+}
+
+// Redc(a a): each cross product once, doubled (301 MADs).  Operand: limbs < 2^29 (header comment), so the doubled
+// limbs are < 2^30 and a column is below 7 * 2^59 + 2^58 + 14 * 2^56 + 2^36 < 2^64.
 BLS_INL fp fp_sqr_body(const fp& a) {
-  fp r;
-  uint32_t m[BLS_NL];
   uint32_t a2[BLS_NL];
 #pragma unroll
   for (int i = 0; i < BLS_NL; i++) a2[i] = a.l[i] << 1;
-  uint64_t acc = 0;
-#pragma unroll
-  for (int k = 0; k < BLS_NL; k++) {
-#pragma unroll
-    for (int i = 0; 2 * i < k; i++) BLS_MAC(acc, a2[i], a.l[k - i]);
-    if ((k & 1) == 0) BLS_MAC(acc, a.l[k >> 1], a.l[k >> 1]);
-#pragma unroll
-    for (int i = 0; i < k; i++) BLS_MAC(acc, m[i], FP_P.l[k - i]);
-    uint32_t mk = ((uint32_t)acc * BLS_N0INV) & BLS_MASK;
-    m[k] = mk;
-    BLS_MAC(acc, mk, FP_P.l[0]);
-    acc >>= BLS_LB;
-  }
-#pragma unroll
-  for (int k = BLS_NL; k < 2 * BLS_NL - 1; k++) {
-#pragma unroll
-    for (int i = k - BLS_NL + 1; 2 * i < k; i++) BLS_MAC(acc, a2[i], a.l[k - i]);
-    if ((k & 1) == 0) BLS_MAC(acc, a.l[k >> 1], a.l[k >> 1]);
-#pragma unroll
-    for (int i = k - BLS_NL + 1; i < BLS_NL; i++) BLS_MAC(acc, m[i], FP_P.l[k - i]);
-    r.l[k - BLS_NL] = (uint32_t)acc & BLS_MASK;
-    acc >>= BLS_LB;
-  }
-  r.l[BLS_NL - 1] = (uint32_t)acc;
-  return r;
+  fp r[1];
+  mont_scan<1>(r, [&](uint64_t* acc, int i, int j) BLS_AB_INL {
+    if (i < j) BLS_MAC(acc[0], a2[i], a.l[j]);
+    if (i == j) BLS_MAC(acc[0], a.l[i], a.l[i]);
+  });
+  return r[0];
 }
 
 // Register-ABI product boundary (see the call-granularity policy above).  BLS_INLINE_PRODUCTS=1 inlines
 // the bodies instead (bigger code, slower compiles; for experiments).
 #if defined(__HIP_DEVICE_COMPILE__) && !BLS_INLINE_PRODUCTS
-struct fp_ret {
-  uint32_t l[BLS_NL];
-};
+typedef fp fp_ret;  // a 14-dword aggregate comes back in VGPRs as it is
 #define BLS_ARGS14(x) \
   x.l[0], x.l[1], x.l[2], x.l[3], x.l[4], x.l[5], x.l[6], x.l[7], x.l[8], x.l[9], x.l[10], x.l[11], x.l[12], x.l[13]
 #define BLS_PARAMS14(x)                                                                                     \
@@ -176,34 +176,14 @@ struct fp_ret {
 #define BLS_INIT14(x) {{x##0, x##1, x##2, x##3, x##4, x##5, x##6, x##7, x##8, x##9, x##10, x##11, x##12, x##13}}
 __device__ __noinline__ fp_ret fp_mul_r(BLS_PARAMS14(a), BLS_PARAMS14(b)) {
   const fp x = BLS_INIT14(a), y = BLS_INIT14(b);
-  const fp r = fp_mul_body(x, y);
-  fp_ret o;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) o.l[i] = r.l[i];
-  return o;
+  return fp_mul_body(x, y);
 }
 __device__ __noinline__ fp_ret fp_sqr_r(BLS_PARAMS14(a)) {
   const fp x = BLS_INIT14(a);
-  const fp r = fp_sqr_body(x);
-  fp_ret o;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) o.l[i] = r.l[i];
-  return o;
+  return fp_sqr_body(x);
 }
-__device__ __forceinline__ fp fp_mul(const fp& a, const fp& b) {
-  const fp_ret t = fp_mul_r(BLS_ARGS14(a), BLS_ARGS14(b));
-  fp r;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) r.l[i] = t.l[i];
-  return r;
-}
-__device__ __forceinline__ fp fp_sqr(const fp& a) {
-  const fp_ret t = fp_sqr_r(BLS_ARGS14(a));
-  fp r;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) r.l[i] = t.l[i];
-  return r;
-}
+__device__ __forceinline__ fp fp_mul(const fp& a, const fp& b) { return fp_mul_r(BLS_ARGS14(a), BLS_ARGS14(b)); }
+__device__ __forceinline__ fp fp_sqr(const fp& a) { return fp_sqr_r(BLS_ARGS14(a)); }
 #else
 BLS_INL fp fp_mul(const fp& a, const fp& b) {
   BLS_COUNT(bls_count_mul);
@@ -218,17 +198,17 @@ BLS_INL fp fp_sqr(const fp& a) {
 // ------------------------------------------------------------------------------------------------
 // Additive operations (keep value <= 2p, limbs normalized)
 // ------------------------------------------------------------------------------------------------
-// s (value <= 4p, normalized) -> s or s - 2p
-BLS_HD fp fp_csub_2p(const fp& s) {
+// s (normalized) -> s - k if that is not negative, else s
+BLS_HD fp fp_csub(const fp& s, const fp& k) {
   fp t;
   int32_t bw = 0;
 #pragma unroll
   for (int i = 0; i < BLS_NL - 1; i++) {
-    int32_t v = (int32_t)s.l[i] - (int32_t)FP_2P.l[i] + bw;
+    int32_t v = (int32_t)s.l[i] - (int32_t)k.l[i] + bw;
     t.l[i] = (uint32_t)v & BLS_MASK;
     bw = v >> BLS_LB;
   }
-  int32_t top = (int32_t)s.l[BLS_NL - 1] - (int32_t)FP_2P.l[BLS_NL - 1] + bw;
+  int32_t top = (int32_t)s.l[BLS_NL - 1] - (int32_t)k.l[BLS_NL - 1] + bw;
   t.l[BLS_NL - 1] = (uint32_t)top;
   const bool neg = top < 0;
   fp r;
@@ -236,19 +216,9 @@ BLS_HD fp fp_csub_2p(const fp& s) {
   for (int i = 0; i < BLS_NL; i++) r.l[i] = neg ? s.l[i] : t.l[i];
   return r;
 }
-
-BLS_HD fp fp_add(const fp& a, const fp& b) {
-  fp s;
-  uint32_t c = 0;
-#pragma unroll
-  for (int i = 0; i < BLS_NL - 1; i++) {
-    uint32_t v = a.l[i] + b.l[i] + c;
-    s.l[i] = v & BLS_MASK;
-    c = v >> BLS_LB;
-  }
-  s.l[BLS_NL - 1] = a.l[BLS_NL - 1] + b.l[BLS_NL - 1] + c;
-  return fp_csub_2p(s);
-}
+// s (value <= 4p, normalized) -> s or s - 2p
+BLS_HD fp fp_csub_2p(const fp& s) { return fp_csub(s, FP_2P); }
+BLS_HD fp fp_csub_p(const fp& s) { return fp_csub(s, FP_P); }
 
 // Un-normalized, un-reduced sum: only as an operand of fp_mul / fp_sqr (see header comment).
 BLS_HD fp fp_add_nr(const fp& a, const fp& b) {
@@ -271,6 +241,8 @@ BLS_HD fp fp_add_norm(const fp& a, const fp& b) {
   s.l[BLS_NL - 1] = a.l[BLS_NL - 1] + b.l[BLS_NL - 1] + c;
   return s;
 }
+
+BLS_HD fp fp_add(const fp& a, const fp& b) { return fp_csub_2p(fp_add_norm(a, b)); }
 
 // 8p with every limb but the top borrowed up into [2^28 - 1, 2^29): a + FP_8P_K - b has no negative limb for any
 // normalized b of value <= 4p (its top limb stays below FP_8P_K's) -- the lazy subtraction below
@@ -348,23 +320,6 @@ BLS_HD fp fp_zero() {
 BLS_HD fp fp_one() { return FP_ONE; }
 
 // Canonical representative in [0, p)
-BLS_HD fp fp_csub_p(const fp& s) {
-  fp t;
-  int32_t bw = 0;
-#pragma unroll
-  for (int i = 0; i < BLS_NL - 1; i++) {
-    int32_t v = (int32_t)s.l[i] - (int32_t)FP_P.l[i] + bw;
-    t.l[i] = (uint32_t)v & BLS_MASK;
-    bw = v >> BLS_LB;
-  }
-  int32_t top = (int32_t)s.l[BLS_NL - 1] - (int32_t)FP_P.l[BLS_NL - 1] + bw;
-  t.l[BLS_NL - 1] = (uint32_t)top;
-  const bool neg = top < 0;
-  fp r;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) r.l[i] = neg ? s.l[i] : t.l[i];
-  return r;
-}
 BLS_HD fp fp_canon(const fp& a) { return fp_csub_p(fp_csub_p(a)); }
 
 // ------------------------------------------------------------------------------------------------

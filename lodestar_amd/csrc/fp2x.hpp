@@ -49,31 +49,12 @@ BLS_HD fp fp_swap(const fp& x) {
 // column bound depends on the limbs only, not on the values (tests/coop_vectors.py fp2x_mul: 8p - 1 per coefficient,
 // and 8p as gtx.hpp's F_add_nr of two 4p sums reaches it).
 BLS_INL fp fp_dot_body(const fp& x1, const fp& y1, const fp& x2, const fp& y2) {
-  uint32_t m[BLS_NL];
-  uint64_t acc = 0;
-  fp r;
-#pragma unroll
-  for (int k = 0; k < 2 * BLS_NL - 1; k++) {
-    const int lo = k < BLS_NL ? 0 : k - BLS_NL + 1, hi = k < BLS_NL ? k : BLS_NL - 1;
-#pragma unroll
-    for (int i = lo; i <= hi; i++) {
-      BLS_MAC(acc, x1.l[i], y1.l[k - i]);
-      BLS_MAC(acc, x2.l[i], y2.l[k - i]);
-    }
-    const int mhi = k < BLS_NL ? k - 1 : BLS_NL - 1;
-#pragma unroll
-    for (int i = lo; i <= mhi; i++) BLS_MAC(acc, m[i], FP_P.l[k - i]);
-    if (k < BLS_NL) {
-      const uint32_t q = ((uint32_t)acc * BLS_N0INV) & BLS_MASK;
-      m[k] = q;
-      BLS_MAC(acc, q, FP_P.l[0]);
-    } else {
-      r.l[k - BLS_NL] = (uint32_t)acc & BLS_MASK;
-    }
-    acc >>= BLS_LB;
-  }
-  r.l[BLS_NL - 1] = (uint32_t)acc;
-  return r;
+  fp r[1];
+  mont_scan<1>(r, [&](uint64_t* acc, int i, int j) BLS_AB_INL {
+    BLS_MAC(acc[0], x1.l[i], y1.l[j]);
+    BLS_MAC(acc[0], x2.l[i], y2.l[j]);
+  });
+  return r[0];
 }
 
 // this lane's coefficient of a * b.  a, b: limbs < 2^29, values <= 8p (normalized values or one fp_add_nr level);
@@ -114,34 +95,16 @@ BLS_INL fp fp2x_sqr_body(const fp& a) {
 // register-ABI calls (fp.hpp call-granularity policy): 28 / 14 VGPR arguments, 14 returned
 __device__ __noinline__ fp_ret fp2x_mul_r(BLS_PARAMS14(a), BLS_PARAMS14(b)) {
   const fp x = BLS_INIT14(a), y = BLS_INIT14(b);
-  const fp r = fp2x_mul_body(x, y);
-  fp_ret o;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) o.l[i] = r.l[i];
-  return o;
+  return fp2x_mul_body(x, y);
 }
 __device__ __noinline__ fp_ret fp2x_sqr_r(BLS_PARAMS14(a)) {
   const fp x = BLS_INIT14(a);
-  const fp r = fp2x_sqr_body(x);
-  fp_ret o;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) o.l[i] = r.l[i];
-  return o;
+  return fp2x_sqr_body(x);
 }
 __device__ __forceinline__ fp2x fp2x_mul(const fp2x& a, const fp2x& b) {
-  const fp_ret t = fp2x_mul_r(BLS_ARGS14(a.v), BLS_ARGS14(b.v));
-  fp2x r;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) r.v.l[i] = t.l[i];
-  return r;
+  return fp2x{fp2x_mul_r(BLS_ARGS14(a.v), BLS_ARGS14(b.v))};
 }
-__device__ __forceinline__ fp2x fp2x_sqr(const fp2x& a) {
-  const fp_ret t = fp2x_sqr_r(BLS_ARGS14(a.v));
-  fp2x r;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) r.v.l[i] = t.l[i];
-  return r;
-}
+__device__ __forceinline__ fp2x fp2x_sqr(const fp2x& a) { return fp2x{fp2x_sqr_r(BLS_ARGS14(a.v))}; }
 #else
 BLS_INL fp2x fp2x_mul(const fp2x& a, const fp2x& b) { return fp2x{fp2x_mul_body(a.v, b.v)}; }
 BLS_INL fp2x fp2x_sqr(const fp2x& a) { return fp2x{fp2x_sqr_body(a.v)}; }

@@ -101,43 +101,17 @@ BLS_CONST fp FP_16P_K = {{0x3ffaaab0, 0x3efffffc, 0x3ffffb9c, 0x3ffeb150, 0x3241
 // accumulator and no operand sums: fewer instruction slots and registers per product.  Inputs as fp2_mul_lazy_body
 // (limbs < 2^29, values <= 8p); column bound 14 (2^58 + 2^59) + 14 * 2^56 + 2^36 < 2^64; outputs normalized, < 1.1 p.
 BLS_INL fp2 fp2_mul_sb_body(const fp& a0, const fp& a1, const fp& b0, const fp& b1) {
-  uint32_t nb[BLS_NL], m0[BLS_NL], m1[BLS_NL];
+  uint32_t nb[BLS_NL];
 #pragma unroll
   for (int i = 0; i < BLS_NL; i++) nb[i] = FP_16P_K.l[i] - b1.l[i];
-  uint64_t acc0 = 0, acc1 = 0;
-  fp2 r;
-#pragma unroll
-  for (int k = 0; k < 2 * BLS_NL - 1; k++) {
-    const int lo = k < BLS_NL ? 0 : k - BLS_NL + 1, hi = k < BLS_NL ? k : BLS_NL - 1;
-#pragma unroll
-    for (int i = lo; i <= hi; i++) {
-      BLS_MAC(acc0, a0.l[i], b0.l[k - i]);
-      BLS_MAC(acc1, a0.l[i], b1.l[k - i]);
-      BLS_MAC(acc0, a1.l[i], nb[k - i]);
-      BLS_MAC(acc1, a1.l[i], b0.l[k - i]);
-    }
-    const int mhi = k < BLS_NL ? k - 1 : BLS_NL - 1;
-#pragma unroll
-    for (int i = lo; i <= mhi; i++) {
-      BLS_MAC(acc0, m0[i], FP_P.l[k - i]);
-      BLS_MAC(acc1, m1[i], FP_P.l[k - i]);
-    }
-    if (k < BLS_NL) {
-      const uint32_t q0 = ((uint32_t)acc0 * BLS_N0INV) & BLS_MASK, q1 = ((uint32_t)acc1 * BLS_N0INV) & BLS_MASK;
-      m0[k] = q0;
-      m1[k] = q1;
-      BLS_MAC(acc0, q0, FP_P.l[0]);
-      BLS_MAC(acc1, q1, FP_P.l[0]);
-    } else {
-      r.c0.l[k - BLS_NL] = (uint32_t)acc0 & BLS_MASK;
-      r.c1.l[k - BLS_NL] = (uint32_t)acc1 & BLS_MASK;
-    }
-    acc0 >>= BLS_LB;
-    acc1 >>= BLS_LB;
-  }
-  r.c0.l[BLS_NL - 1] = (uint32_t)acc0;
-  r.c1.l[BLS_NL - 1] = (uint32_t)acc1;
-  return r;
+  fp r[2];
+  mont_scan<2>(r, [&](uint64_t* acc, int i, int j) BLS_AB_INL {
+    BLS_MAC(acc[0], a0.l[i], b0.l[j]);
+    BLS_MAC(acc[1], a0.l[i], b1.l[j]);
+    BLS_MAC(acc[0], a1.l[i], nb[j]);
+    BLS_MAC(acc[1], a1.l[i], b0.l[j]);
+  });
+  return fp2_make(r[0], r[1]);
 }
 #ifndef BLS_FP2_SB
 #define BLS_FP2_SB 1
@@ -148,55 +122,22 @@ BLS_INL fp2 fp2_mul_sb_body(const fp& a0, const fp& a1, const fp& b0, const fp& 
 #define fp2_mul_body_sel fp2_mul_lazy_body
 #endif
 
-// Fp2 squaring (complex method): c0 = (a0 + a1)(a0 - a1), c1 = 2 a0 a1 -- two independent products.  Input:
-// normalized limbs, values <= 4p (stored values, or fp2_add_norm of two); a0 - a1 goes to the product as
-// a0 + 8p - a1 (fp_sub_k8, no reduction), so an input above 2p never underflows.  Outputs < 1.05 p.
-#if defined(__HIP_DEVICE_COMPILE__)
 // (Redc(x0 y0), Redc(x1 y1)): fp_mul_body twice, written column by column over two accumulators so the two chains
 // of fp2_sqr_r stay interleaved and each result ends in the registers it is returned in (two fp_mul_body in a row
 // cost 14 v_mov there; fp2_mul_fp_r, whose products share an operand, is as short with two and needs fewer VGPRs).
 // It holds both operand sets and both m arrays at once: fp2_sqr_r takes 132 VGPRs where it took 114.
 // Operands and outputs as fp_mul_body; the same integers, limb for limb.
 BLS_INL fp2 fp_mul_pair_body(const fp& x0, const fp& y0, const fp& x1, const fp& y1) {
-  uint32_t m0[BLS_NL], m1[BLS_NL];
-  uint64_t acc0 = 0, acc1 = 0;
-  fp2 r;
-#pragma unroll
-  for (int k = 0; k < 2 * BLS_NL - 1; k++) {
-    const int lo = k < BLS_NL ? 0 : k - BLS_NL + 1, hi = k < BLS_NL ? k : BLS_NL - 1;
-#pragma unroll
-    for (int i = lo; i <= hi; i++) {
-      BLS_MAC(acc0, x0.l[i], y0.l[k - i]);
-      BLS_MAC(acc1, x1.l[i], y1.l[k - i]);
-    }
-    const int mhi = k < BLS_NL ? k - 1 : BLS_NL - 1;
-#pragma unroll
-    for (int i = lo; i <= mhi; i++) {
-      BLS_MAC(acc0, m0[i], FP_P.l[k - i]);
-      BLS_MAC(acc1, m1[i], FP_P.l[k - i]);
-    }
-    if (k < BLS_NL) {
-      const uint32_t q0 = ((uint32_t)acc0 * BLS_N0INV) & BLS_MASK, q1 = ((uint32_t)acc1 * BLS_N0INV) & BLS_MASK;
-      m0[k] = q0;
-      m1[k] = q1;
-      BLS_MAC(acc0, q0, FP_P.l[0]);
-      BLS_MAC(acc1, q1, FP_P.l[0]);
-    } else {
-      r.c0.l[k - BLS_NL] = (uint32_t)acc0 & BLS_MASK;
-      r.c1.l[k - BLS_NL] = (uint32_t)acc1 & BLS_MASK;
-    }
-    acc0 >>= BLS_LB;
-    acc1 >>= BLS_LB;
-  }
-  r.c0.l[BLS_NL - 1] = (uint32_t)acc0;
-  r.c1.l[BLS_NL - 1] = (uint32_t)acc1;
-  return r;
+  fp r[2];
+  mont_scan<2>(r, [&](uint64_t* acc, int i, int j) BLS_AB_INL {
+    BLS_MAC(acc[0], x0.l[i], y0.l[j]);
+    BLS_MAC(acc[1], x1.l[i], y1.l[j]);
+  });
+  return fp2_make(r[0], r[1]);
 }
-#else
-BLS_INL fp2 fp_mul_pair_body(const fp& x0, const fp& y0, const fp& x1, const fp& y1) {
-  return fp2_make(fp_mul_body(x0, y0), fp_mul_body(x1, y1));
-}
-#endif
+// Fp2 squaring (complex method): c0 = (a0 + a1)(a0 - a1), c1 = 2 a0 a1 -- two independent products.  Input:
+// normalized limbs, values <= 4p (stored values, or fp2_add_norm of two); a0 - a1 goes to the product as
+// a0 + 8p - a1 (fp_sub_k8, no reduction), so an input above 2p never underflows.  Outputs < 1.05 p.
 BLS_INL fp2 fp2_sqr_body(const fp2& a) {
   return fp_mul_pair_body(fp_add_nr(a.c0, a.c1), fp_sub_k8(a.c0, a.c1), fp_add_nr(a.c0, a.c0), a.c1);
 }
@@ -218,26 +159,7 @@ __shared__ uint32_t bls_fp2_arg[2 * BLS_NL * BLS_FP2_LDS_LANES];
 // The 28-dword result comes back in VGPRs as a 32-wide vector: clang's AMDGPU ABI returns an aggregate of more than
 // 16 dwords indirectly (through a scratch sret slot: 7 dwordx4 stores + 7 loads per call), a vector type directly.
 typedef uint32_t fp2_ret __attribute__((ext_vector_type(32)));
-__device__ __noinline__ fp2_ret fp2_mul_r(BLS_PARAMS14(a), BLS_PARAMS14(c)) {
-  const fp x0 = BLS_INIT14(a), x1 = BLS_INIT14(c);
-  const uint32_t t = threadIdx.x;
-  fp y0, y1;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) {
-    y0.l[i] = bls_fp2_arg[i * BLS_FP2_LDS_LANES + t];
-    y1.l[i] = bls_fp2_arg[(BLS_NL + i) * BLS_FP2_LDS_LANES + t];
-  }
-  const fp2 r = fp2_mul_body_sel(x0, x1, y0, y1);
-  fp2_ret o;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) {
-    o[i] = r.c0.l[i];
-    o[BLS_NL + i] = r.c1.l[i];
-  }
-  return o;
-}
-__device__ __noinline__ fp2_ret fp2_sqr_r(BLS_PARAMS14(a), BLS_PARAMS14(c)) {
-  const fp2 r = fp2_sqr_body(fp2_make(BLS_INIT14(a), BLS_INIT14(c)));
+__device__ __forceinline__ fp2_ret fp2_to_ret(const fp2& r) {
   fp2_ret o;
 #pragma unroll
   for (int i = 0; i < BLS_NL; i++) {
@@ -254,6 +176,20 @@ __device__ __forceinline__ fp2 fp2_from_ret(const fp2_ret& o) {
     r.c1.l[i] = o[BLS_NL + i];
   }
   return r;
+}
+__device__ __noinline__ fp2_ret fp2_mul_r(BLS_PARAMS14(a), BLS_PARAMS14(c)) {
+  const fp x0 = BLS_INIT14(a), x1 = BLS_INIT14(c);
+  const uint32_t t = threadIdx.x;
+  fp y0, y1;
+#pragma unroll
+  for (int i = 0; i < BLS_NL; i++) {
+    y0.l[i] = bls_fp2_arg[i * BLS_FP2_LDS_LANES + t];
+    y1.l[i] = bls_fp2_arg[(BLS_NL + i) * BLS_FP2_LDS_LANES + t];
+  }
+  return fp2_to_ret(fp2_mul_body_sel(x0, x1, y0, y1));
+}
+__device__ __noinline__ fp2_ret fp2_sqr_r(BLS_PARAMS14(a), BLS_PARAMS14(c)) {
+  return fp2_to_ret(fp2_sqr_body(fp2_make(BLS_INIT14(a), BLS_INIT14(c))));
 }
 __device__ __forceinline__ fp2 fp2_mul(const fp2& a, const fp2& b) {
   const uint32_t t = threadIdx.x;
@@ -277,14 +213,7 @@ __device__ __noinline__ fp2_ret fp2_mul_fp_r(BLS_PARAMS14(a), BLS_PARAMS14(c)) {
   fp y;
 #pragma unroll
   for (int i = 0; i < BLS_NL; i++) y.l[i] = bls_fp2_arg[i * BLS_FP2_LDS_LANES + t];
-  const fp r0 = fp_mul_body(x0, y), r1 = fp_mul_body(x1, y);
-  fp2_ret o;
-#pragma unroll
-  for (int i = 0; i < BLS_NL; i++) {
-    o[i] = r0.l[i];
-    o[BLS_NL + i] = r1.l[i];
-  }
-  return o;
+  return fp2_to_ret(fp2_make(fp_mul_body(x0, y), fp_mul_body(x1, y)));
 }
 __device__ __forceinline__ fp2 fp2_mul_fp(const fp2& a, const fp& s) {
   const uint32_t t = threadIdx.x;
