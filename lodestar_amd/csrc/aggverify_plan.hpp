@@ -16,7 +16,11 @@
 
 namespace aggverify_plan {
 
-constexpr uint32_t kCoopMax = 512;   // Miller items up to which a call takes the cooperative forms (as the same-message call)
+// Miller items up to which a call takes the cooperative forms: same_plan::kCoopMax (helpers.cpp asserts it)
+constexpr uint32_t kCoopMax = 512;
+// The message index's key (run_plan.hpp dedupe_messages).  The call draws no randomness, so it is a constant: the key
+// only spreads the table's probes, equality is by memcmp.
+constexpr uint64_t kMsgKey = 0xbb67ae8584caa73bull;
 constexpr uint32_t kLaneChunk = 8;   // most items per accumulator in the lane form; the cooperative form has one
 constexpr uint32_t kLaneReduceMax = 8;  // chunks per job, on average, up to which one lane multiplies a job's chunk values
 
@@ -77,6 +81,26 @@ inline Plan build(const uint32_t* job_first, uint32_t n_jobs, const uint8_t* pla
     const auto r = miller_plan::add_chunks(p.chunk_first, p.chunk_items, a, e, k, false, p.items.data());
     p.f_ranges[2 * (size_t)j] = r.first, p.f_ranges[2 * (size_t)j + 1] = r.second;
   }
+  return p;
+}
+
+// What a call decides before the device has decoded anything.  Every non-empty job is planned: which of them the
+// device rejects is known only after the decodes, and their items are switched off by the include bytes (one
+// synchronize less than reading the status back first).
+struct CallPlan {
+  Counts planned;
+  bool lane, lane_reduce;  // the forms; one lane, not one wave, multiplies a job's chunk values (jobs of few chunks)
+  uint32_t k, n_chunks;    // items per chunk, chunks
+  Plan plan;
+};
+inline CallPlan plan_call(const uint32_t* job_first, uint32_t n_jobs, bool lane_flag) {
+  CallPlan p;
+  p.planned = count(job_first, n_jobs, nullptr, 1);
+  p.lane = form(p.planned.items, lane_flag) != 0;
+  p.k = chunk_items_for(job_first, n_jobs, p.lane ? 1 : 0, lane_flag);
+  p.plan = build(job_first, n_jobs, nullptr, p.k);
+  p.n_chunks = p.plan.n_chunks();
+  p.lane_reduce = p.lane && (uint64_t)p.n_chunks <= (uint64_t)kLaneReduceMax * p.planned.jobs;
   return p;
 }
 

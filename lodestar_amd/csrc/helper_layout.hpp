@@ -57,6 +57,22 @@ struct SameInput {
   }
 };
 
+// The message branch of the same-message calls and of blsgpu_aggregate_verify, M G2 columns wide, in d_work (words):
+// batch-inverse scratch | H(m) affine | Jacobian | its norm | the map's scratch | the cofactor clearing's.  hl::Same and
+// hl::AggVerify carve it here and keep the six offsets as their fields w_minv .. w_hq; msg() hands them on as one.
+struct MsgBranch {
+  size_t inv, h_aff, h_jac, h_norm, h_prep, h_q;
+  MsgBranch(size_t a, size_t b, size_t c, size_t d, size_t e, size_t f)
+      : inv(a), h_aff(b), h_jac(c), h_norm(d), h_prep(e), h_q(f) {}
+  MsgBranch(Carve& w, size_t M) {
+    inv = w.take(M * kFp), h_aff = w.take(M * kG2A), h_jac = w.take(M * kG2J), h_norm = w.take(M * kFp);
+    h_prep = w.take(M * 14 * kFp), h_q = w.take(M * 2 * kG2J);
+  }
+  void put(size_t& a, size_t& b, size_t& c, size_t& d, size_t& e, size_t& f) const {
+    a = inv, b = h_aff, c = h_jac, d = h_norm, e = h_prep, f = h_q;
+  }
+};
+
 // blsgpu_aggregate_with_randomness.  d_in: the shared inputs | out_pk | out_sig | first_bad | error indices | group
 // status | error codes | signature status | signature flags (the b_ fields are those hl::Same keeps in d_bytes).
 // d_work: sig_aff | window scratch | sum_pk | sum_sig.
@@ -81,13 +97,14 @@ struct Awr {
 //   d_bytes: error indices | error codes | signature status | signature flags | message flags | group include |
 //            group code | group verdict | group_result | set_result
 //   d_work:  sig_aff | window scratch of the G2 sum | of the G1 sum | sum_pk | sum_sig | pk_aff | 1 / z | F | G |
-//            message branch (inv, h_aff, h_jac, h_norm, h_prep, h_q);  d_lines: the messages' Miller lines
+//            message branch (msg(), U columns);  d_lines: the messages' Miller lines
 struct Same {
   SameInput in;
   size_t umsg, gmsg, iota, in_total;
   size_t b_ek, b_ec, b_st, b_fl, b_mf, b_inc, b_code, b_ok, b_gres, b_sres, bytes_total;
   size_t w_tab, w_tab_pk, w_sum_pk, w_sum_sig, w_pk_aff, w_inv, w_F, w_G;
   size_t w_minv, w_haff, w_hjac, w_hnorm, w_hprep, w_hq, work_words, lines_words;
+  MsgBranch msg() const { return MsgBranch(w_minv, w_haff, w_hjac, w_hnorm, w_hprep, w_hq); }
   Same(size_t G, size_t n, size_t U, size_t sig_stride, bool keys_are_bytes, size_t lanes) {
     Carve c, b, w{1};
     in = SameInput(c, G, n, sig_stride, keys_are_bytes);
@@ -99,8 +116,7 @@ struct Same {
     w_tab = w.take(lanes * kAwrTabWords), w_tab_pk = w.take(lanes * kAwrTabWords);
     w_sum_pk = w.take(G * kG1J), w_sum_sig = w.take(G * kG2J), w_pk_aff = w.take(G * kG1A);
     w_inv = w.take(G * kFp), w_F = w.take(G * kFp12), w_G = w.take(G * kFp12);
-    w_minv = w.take(U * kFp), w_haff = w.take(U * kG2A), w_hjac = w.take(U * kG2J), w_hnorm = w.take(U * kFp);
-    w_hprep = w.take(U * 14 * kFp), w_hq = w.take(U * 2 * kG2J);
+    MsgBranch(w, U).put(w_minv, w_haff, w_hjac, w_hnorm, w_hprep, w_hq);
     work_words = w.end, lines_words = U * kMillerLineWords;
   }
 };
@@ -164,13 +180,14 @@ struct SameAgg {
 //            f_ranges (a job's chunk range) | kv96 (the validated keys, 96 bytes each)
 //   d_bytes: signature status | signature flags | KeyValidate status | pair code | message flags | include | checked |
 //            job code | verdict | job_result | first_bad
-//   d_work:  sig_aff | pk_aff | msg_idx | f_chunk | F | message branch (inv, h_aff, h_jac, h_norm, h_prep, h_q)
+//   d_work:  sig_aff | pk_aff | msg_idx | f_chunk | F | message branch (msg(), M columns)
 //   d_lines: the Miller lines of the M columns (lane form)
 struct AggVerify {
   size_t T, M, key_bytes;
   size_t gf, len, sigs, keys, umsg, pmsg, cf, ci, fr, kv96, in_total;
   size_t b_st, b_fl, b_kv, b_code, b_mf, b_inc, b_chk, b_jcode, b_ok, b_res, b_fb, bytes_total;
   size_t w_pk_aff, w_midx, w_fchunk, w_F, w_minv, w_haff, w_hjac, w_hnorm, w_hprep, w_hq, work_words, lines_words;
+  MsgBranch msg() const { return MsgBranch(w_minv, w_haff, w_hjac, w_hnorm, w_hprep, w_hq); }
   AggVerify(size_t J, size_t n, size_t U, size_t C, size_t sig_stride, bool keys_are_bytes, size_t pk_len,
             bool validate) {
     Carve c, b, w{1};
@@ -184,8 +201,7 @@ struct AggVerify {
     bytes_total = b.at;
     w.take(J * kG2A);  // sig_aff, at 0
     w_pk_aff = w.take(T * kG1A), w_midx = w.take(T), w_fchunk = w.take(T * kFp12), w_F = w.take(J * kFp12);
-    w_minv = w.take(M * kFp), w_haff = w.take(M * kG2A), w_hjac = w.take(M * kG2J), w_hnorm = w.take(M * kFp);
-    w_hprep = w.take(M * 14 * kFp), w_hq = w.take(M * 2 * kG2J);
+    MsgBranch(w, M).put(w_minv, w_haff, w_hjac, w_hnorm, w_hprep, w_hq);
     work_words = w.end, lines_words = M * kMillerLineWords;
   }
 };

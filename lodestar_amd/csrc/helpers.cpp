@@ -3,16 +3,22 @@
 // table_stream, in Device::helper's buffers; helper_call is the envelope they share and helper_layout.hpp says where
 // every field of their device arenas lies.  The asynchronous verification pipeline is runtime.cpp and pipeline.cpp.
 #include "aggverify_plan.hpp"
+#include "helper_buffers.hpp"
 #include "helper_layout.hpp"
 #include "runtime_internal.hpp"
+#include "same_plan.hpp"
 
 using namespace blsgpu_rt;
 namespace hl = helper_layout;
 namespace avp = aggverify_plan;
+namespace sp = same_plan;
 
 static_assert(hl::kFp == W_FP && hl::kG1A == W_G1A && hl::kG1J == W_G1J && hl::kG2A == W_G2A && hl::kG2J == W_G2J &&
                   hl::kFp12 == W_FP12 && hl::kAwrTabWords == AWR_TAB_WORDS && hl::kMillerLineWords == kMillerLineWords,
               "helper_layout.hpp restates the element widths of kernels.h");
+static_assert(sp::kBlockGroups == SAME_BLOCK_GROUPS && sp::kBlockGroups == 1024,
+              "same_plan.hpp restates the block size of kernels.h; include/blsgpu.h documents blocks of 1024 groups");
+static_assert(avp::kCoopMax == sp::kCoopMax, "one form threshold for the same-message calls and AggregateVerify");
 
 namespace {
 
@@ -51,18 +57,26 @@ struct Grouped {
   uint32_t n = 0;  // group_first[G], set by check_group_layout
 };
 
-// BLSGPU_OK and a.n, or BLSGPU_ERR_ARGS: group_first starts at 0 and never decreases, at most 2^20 signatures, and
-// no 192-byte signature under a stride below 192.
-int check_group_layout(Grouped& a) {
-  if (a.group_first[0] != 0) return BLSGPU_ERR_ARGS;
-  for (uint32_t g = 0; g < a.G; g++)
-    if (a.group_first[g + 1] < a.group_first[g]) return BLSGPU_ERR_ARGS;
-  a.n = a.group_first[a.G];
-  if (a.n > (1u << 20)) return BLSGPU_ERR_ARGS;
-  if (a.sig_stride < 192)
-    for (uint32_t k = 0; k < a.n; k++)
-      if (a.sig_len[k] == 192) return BLSGPU_ERR_ARGS;
+// BLSGPU_OK and total = first[count], or BLSGPU_ERR_ARGS: the offsets start at 0, never decrease and end at most at
+// 2^20 (group_first of the grouped calls, job_first of blsgpu_aggregate_verify).
+int check_offsets(const uint32_t* first, uint32_t count, uint32_t& total) {
+  if (first[0] != 0) return BLSGPU_ERR_ARGS;
+  for (uint32_t g = 0; g < count; g++)
+    if (first[g + 1] < first[g]) return BLSGPU_ERR_ARGS;
+  total = first[count];
+  return total > (1u << 20) ? BLSGPU_ERR_ARGS : BLSGPU_OK;
+}
+// BLSGPU_ERR_ARGS for a 192-byte signature under a stride below 192
+int check_sig_lens(const uint32_t* sig_len, uint32_t n_sigs, uint32_t sig_stride) {
+  if (sig_stride < 192)
+    for (uint32_t k = 0; k < n_sigs; k++)
+      if (sig_len[k] == 192) return BLSGPU_ERR_ARGS;
   return BLSGPU_OK;
+}
+// BLSGPU_OK and a.n, or BLSGPU_ERR_ARGS: both checks on a grouped call's signatures
+int check_group_layout(Grouped& a) {
+  if (int e = check_offsets(a.group_first, a.G, a.n)) return e;
+  return check_sig_lens(a.sig_len, a.n, a.sig_stride);
 }
 
 // What both same-message calls refuse before anything is written or reaches the device: no entropy for the call's
@@ -133,6 +147,468 @@ AwrBuffers same_inputs(Device& d, const Grouped& a, const Layout& l, uint8_t* by
   ab.err_k = reinterpret_cast<uint32_t*>(bytes + l.b_ek);
   ab.err_c = reinterpret_cast<int8_t*>(bytes + l.b_ec);
   return ab;
+}
+
+// ---- what blsgpu_verify_same_message and blsgpu_aggregate_verify share ----------------------------------------
+// (their messages are deduplicated and packed by unique_messages, run_plan.hpp.)  The three branches of such a call: signatures on the helper stream s, keys on sb, messages on sc (all s when
+// `serial`: BLSGPU_SAME_SERIAL, diagnostics of the same-message call).  Device::same_st and same_ev are created by
+// the first call that needs them.
+struct Branches {
+  hipStream_t s, sb, sc;
+  bool serial;
+  hipEvent_t* ev;
+};
+Branches branches(Device& d, hipStream_t s, bool serial) {
+  if (!d.same_st[0]) {
+    for (auto& e : d.same_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK(hipStreamCreateWithFlags(&d.same_st[1], hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&d.same_st[0], hipStreamNonBlocking));
+  }
+  return Branches{s, serial ? s : d.same_st[0], serial ? s : d.same_st[1], serial, d.same_ev};
+}
+// Forks sb and sc from what s holds (the input copy), enqueues a on s, b on sb and c on sc, and joins both into s
+template <class A, class B, class C>
+void three_branches(const Branches& br, A a, B b, C c) {
+  HIPCHK(hipEventRecord(br.ev[0], br.s));
+  if (!br.serial) {
+    HIPCHK(hipStreamWaitEvent(br.sb, br.ev[0], 0));
+    HIPCHK(hipStreamWaitEvent(br.sc, br.ev[0], 0));
+  }
+  a(br.s);
+  b(br.sb);
+  HIPCHK(hipEventRecord(br.ev[1], br.sb));
+  c(br.sc);
+  HIPCHK(hipEventRecord(br.ev[2], br.sc));
+  if (!br.serial) {
+    HIPCHK(hipStreamWaitEvent(br.s, br.ev[1], 0));
+    HIPCHK(hipStreamWaitEvent(br.s, br.ev[2], 0));
+  }
+}
+// Runs body(sized); body sets `sized` once the call's buffers have their sizes, that is before its first launch.  On
+// a HIP failure after that no branch may outlive the call -- the next helper call reuses, and may grow, the buffers
+// they work on -- so all three streams are drained before the error goes on to helper_call.
+template <class Body>
+void drained_on_error(Device& d, Body body) {
+  bool sized = false;
+  try {
+    body(sized);
+  } catch (HipError&) {
+    if (sized) {
+      (void)hipStreamSynchronize(d.table_stream);
+      for (hipStream_t x : d.same_st)
+        if (x) (void)hipStreamSynchronize(x);
+    }
+    throw;
+  }
+}
+
+// The message branch (pm: msg_branch, helper_buffers.hpp): H(m) affine (cooperative hashing for few messages, as small verification runs) and, for the lane forms, its lines
+void launch_msg_branch(const PipelineBuffers& pm, bool lines, hipStream_t s) {
+  launch_hash_to_g2(pm, s, pm.n_umsg <= 4096, false);
+  launch_h_affine(pm, s);
+  if (lines) launch_miller_lines2(pm, s);
+}
+
+// ---- one-call same-message verification (the host decisions are same_plan.hpp) ---------
+// diagnostics (tools/bench_same_message.py): the three branches of the group phase on one stream
+inline bool same_serial() {
+  static const bool on = [] {
+    const char* v = getenv("BLSGPU_SAME_SERIAL");
+    return v && v[0] == '1';
+  }();
+  return on;
+}
+// The aggregate outputs of blsgpu_verify_same_message_agg; blsgpu_verify_same_message has none.
+struct SameAggOut {
+  const uint8_t* include;  // [n_sets], nullable
+  uint8_t* out_sig;
+  uint32_t out_sig_len;
+  uint32_t* count;
+};
+// One same-message call on the device: its sizes and streams and where the group phase's fields lie (hl::Same).
+struct SameCall {
+  uint32_t G, n, flags, L;  // L: lanes of the randomized sums
+  Branches br;
+  PipelineBuffers pb, pm;  // the signature decode, the message branch
+  AwrBuffers ab, ab_pk;    // the randomized sums S_g (ab.sum_sig) and P_g (ab.sum_pk; its own window scratch)
+  uint32_t *pk_aff, *inv, *F, *Gs;  // per group: the affine P_g, 1 / z of P_g, the Miller value, MillerLoop(-g1, S_g)
+  uint8_t *inc, *ok;                // per group: include flag, verdict
+  int8_t *code, *gres, *sres;       // per group: code, group_result; per set: set_result
+  const uint32_t *gmsg, *iota;      // per group: message index; 0, 1, .., G
+  bool lane(uint32_t n_items) const { return sp::form(n_items, flags) != 0; }
+};
+// Copies the call's inputs to d_in (hl::Same `l`) and says where everything of the group phase lies.
+SameCall same_upload(Device& d, const Branches& br, const Grouped& a, uint32_t flags, const hl::Same& l, uint32_t L,
+                     uint32_t lanes, const uint64_t* words, const std::vector<uint8_t>& umsgs, const uint32_t* gmsg,
+                     const uint32_t* iota) {
+  Slot& sl = d.helper;
+  uint8_t* din = sl.d_in.p;
+  uint8_t* db = sl.d_bytes.p;
+  uint32_t* w = sl.d_work.p;
+  const uint32_t G = a.G, U = (uint32_t)(umsgs.size() / 32);
+  SameCall c{};
+  c.G = G, c.n = a.n, c.flags = flags, c.L = L, c.br = br;
+  c.ab = same_inputs(d, a, l, db, words, lanes, br.s, c.pb);
+  HIPCHK(hipMemcpyAsync(din + l.umsg, umsgs.data(), (size_t)U * 32, hipMemcpyHostToDevice, br.s));
+  HIPCHK(hipMemcpyAsync(din + l.gmsg, gmsg, (size_t)G * 4, hipMemcpyHostToDevice, br.s));
+  HIPCHK(hipMemcpyAsync(din + l.iota, iota, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, br.s));
+  c.ab_pk = c.ab;  // the G1 sum runs beside the G2 sum: its own window scratch
+  c.ab_pk.tab = w + l.w_tab_pk;
+  c.pm = msg_branch(sl, l.msg(), din + l.umsg, U, U, db + l.b_mf);
+  c.pk_aff = w + l.w_pk_aff, c.inv = w + l.w_inv, c.F = w + l.w_F, c.Gs = w + l.w_G;
+  c.inc = db + l.b_inc, c.ok = db + l.b_ok;
+  c.code = reinterpret_cast<int8_t*>(db + l.b_code);
+  c.gres = reinterpret_cast<int8_t*>(db + l.b_gres);
+  c.sres = reinterpret_cast<int8_t*>(db + l.b_sres);
+  c.gmsg = reinterpret_cast<uint32_t*>(din + l.gmsg);
+  c.iota = reinterpret_cast<uint32_t*>(din + l.iota);
+  return c;
+}
+
+// Miller values and checks of one phase, in two halves.  Miller half: item i < n_items pairs pk_aff[i] (W_G1A, stride
+// n_items) with H(msg_idx[i]) when include[i], F_i (W_FP12, stride n_items).  iota = 0, 1, .., n_items: one item per
+// Miller chunk.  Check half: ok[i] = FinalExp(F_i * MillerLoop(-g1, S_i)) == 1 with S (W_G2J, stride n_items).
+// Cooperative form: k_miller_coop, and k_group_check with its own Miller loop.  Lane form: the messages' stored lines
+// (pm.lines), k_miller_acc6 (six lanes per pairing), MillerLoop(-g1, S) on one lane per item (into Gs) and the final
+// exponentiation on six (k_group_check6).
+void same_miller_half(const PipelineBuffers& pm, uint32_t n_items, const uint32_t* iota, uint32_t* pk_aff,
+                      uint8_t* include, const uint32_t* msg_idx, uint32_t* F, bool lane, hipStream_t s) {
+  PipelineBuffers pb = pm;
+  pb.n = n_items;
+  pb.pk_aff = pk_aff;
+  pb.include = include;
+  pb.msg_idx = msg_idx;
+  pb.n_chunks = n_items;
+  pb.chunk_first = iota;
+  pb.chunk_items = iota;
+  pb.f_chunk = F;
+  if (!lane)
+    launch_miller_coop(pb, false, s, false);
+  else
+    launch_miller_acc6(pb, false, s);
+}
+void same_check_half(uint32_t n_items, const uint32_t* S, const uint32_t* F, uint32_t* Gs, uint8_t* ok, bool lane,
+                     hipStream_t s) {
+  if (!lane) {
+    launch_group_check(S, F, n_items, ok, s);
+  } else {
+    launch_group_sig_miller(S, n_items, Gs, s, false, true);
+    launch_group_check6(F, Gs, n_items, ok, s);
+  }
+}
+
+// Group phase, first part: three branches from the input copy, joined into s, then every group's item.
+void same_group_items(const SameCall& c) {
+  three_branches(
+      c.br,
+      [&](hipStream_t s) {  // signatures: decode + subgroup check (cooperative for small calls), S_g
+        launch_sig_decode(c.pb, c.n, s, c.n <= 4096, nullptr, false, true);
+        launch_awr_sum_sig(c.ab, c.L, s);
+      },
+      [&](hipStream_t sb) {  // keys: P_g and the batch inverses of its z
+        launch_awr_sum_pk(c.ab_pk, c.L, sb);
+        launch_batch_inv(c.ab.sum_pk, c.G, 2 * W_FP, c.inv, c.G, sb);
+      },
+      [&](hipStream_t sc) {  // messages: H(m) affine, and in the lane form its Miller lines
+        launch_msg_branch(c.pm, c.lane(c.G), sc);
+      });
+  launch_same_group_items(c.ab, c.inv, c.pk_aff, c.inc, c.code, c.br.s);
+}
+// Group phase without blocks: one pairing check per group.  Ends synchronized, group_result in h_grp.
+void same_group_checks(const SameCall& c, int8_t* h_grp) {
+  hipStream_t s = c.br.s;
+  same_miller_half(c.pm, c.G, c.iota, c.pk_aff, c.inc, c.gmsg, c.F, c.lane(c.G), s);
+  same_check_half(c.G, c.ab.sum_sig, c.F, c.Gs, c.ok, c.lane(c.G), s);
+  launch_same_group_results(c.ab.group_first, c.G, c.n, c.inc, c.code, c.ok, c.sres, c.gres, s);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h_grp, c.gres, c.G, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
+}
+// Block phase: F_b, S_b per block of groups and one check per block.  S_b needs the sums and the
+// include flags only: it runs on sb, beside the Miller loops, and is joined into s before the check.  Ends
+// synchronized: h_any, h_ok per block, h_inc and h_grp per group.
+void same_block_phase(const SameCall& c, Slot& sl, const hl::SameBlocks& lb, uint32_t NB, uint8_t* h_any,
+                      uint8_t* h_ok, uint8_t* h_inc, int8_t* h_grp) {
+  hipStream_t s = c.br.s, sb = c.br.sb;
+  uint32_t* bw = sl.d_msmW.p;
+  uint32_t* b_F = bw + lb.w_F;
+  uint32_t* b_S = bw + lb.w_S;
+  uint8_t* b_any = sl.d_res.p + lb.b_any;
+  uint8_t* b_ok = sl.d_res.p + lb.b_ok;
+  HIPCHK(hipEventRecord(c.br.ev[0], s));
+  if (!c.br.serial) HIPCHK(hipStreamWaitEvent(sb, c.br.ev[0], 0));
+  launch_same_block_sum(c.ab.sum_sig, c.inc, c.G, NB, b_S, b_any, sb);
+  HIPCHK(hipEventRecord(c.br.ev[1], sb));
+  same_miller_half(c.pm, c.G, c.iota, c.pk_aff, c.inc, c.gmsg, c.F, c.lane(c.G), s);
+  launch_same_block_prod(c.F, c.inc, c.G, NB, bw + lb.w_T0, bw + lb.w_T1, b_F, s);
+  if (!c.br.serial) HIPCHK(hipStreamWaitEvent(s, c.br.ev[1], 0));
+  same_check_half(NB, b_S, b_F, bw + lb.w_G, b_ok, c.lane(NB), s);
+  launch_same_block_results(c.ab.group_first, c.G, c.n, c.inc, c.code, b_any, b_ok, c.sres, c.gres, s);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h_any, b_any, NB, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h_ok, b_ok, NB, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h_inc, c.inc, c.G, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h_grp, c.gres, c.G, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
+}
+// Descent: the listed groups (same_plan::descent_list), each checked from its own F_g, S_g in the descent's buffers
+// (hl::SameBlocks `ld`).  Ends synchronized, h_grp rewritten.
+void same_descent(const SameCall& c, Slot& sl, const hl::SameBlocks& ld, const std::vector<uint32_t>& listed,
+                  int8_t* h_grp) {
+  hipStream_t s = c.br.s;
+  const uint32_t nl = (uint32_t)listed.size();
+  uint32_t* dw = sl.d_fkeep.p;
+  uint8_t* l_ok = sl.d_fbflags.p;
+  HIPCHK(hipMemcpyAsync(dw + ld.d_list, listed.data(), (size_t)nl * 4, hipMemcpyHostToDevice, s));
+  launch_same_gather(c.F, c.ab.sum_sig, c.G, dw + ld.d_list, nl, dw + ld.d_F, dw + ld.d_S, s);
+  same_check_half(nl, dw + ld.d_S, dw + ld.d_F, dw + ld.d_G, l_ok, c.lane(nl), s);
+  launch_same_descent_results(c.ab.group_first, c.G, c.n, dw + ld.d_list, nl, l_ok, c.sres, c.gres, s);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h_grp, c.gres, c.G, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+}
+// Retry phase: the listed sets (same_plan::retry_list), each on its own with r = 1, in the retry buffers (hl::SameRetry
+// `r`; riota = 0, 1, .., nr).  build_lines: the lane forms' lines are not there yet.  Enqueued only.
+// (the driver calls it after a synchronize: none of these is in use by an earlier phase)
+void grow_retry_buffers(Slot& sl, const hl::SameRetry& r, bool lane) {
+  sl.d_list.ensure(r.list_words);
+  sl.d_ok.ensure(r.ok_bytes);
+  sl.d_fb.ensure(r.fb_words);
+  sl.d_S.ensure(r.S_words);
+  sl.d_F.ensure(r.F_words);
+  if (lane) sl.d_G.ensure(r.F_words);
+}
+void same_retry_phase(const SameCall& c, Slot& sl, const hl::SameRetry& r, const sp::Retry& rt,
+                      const std::vector<uint32_t>& riota, bool build_lines) {
+  hipStream_t s = c.br.s;
+  const uint32_t nr = (uint32_t)rt.sets.size();
+  const bool lane = c.lane(nr);
+  uint32_t* dl = sl.d_list.p;
+  HIPCHK(hipMemcpyAsync(dl, rt.sets.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dl + r.msg, rt.msg.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dl + r.iota, riota.data(), (size_t)(nr + 1) * 4, hipMemcpyHostToDevice, s));
+  uint8_t* r_inc = sl.d_ok.p;
+  int8_t* r_code = reinterpret_cast<int8_t*>(sl.d_ok.p + r.code);
+  uint8_t* r_ok = sl.d_ok.p + r.ok;
+  launch_same_retry_items(c.ab, dl, nr, sl.d_fb.p, sl.d_S.p, r_inc, r_code, s);
+  if (build_lines) launch_miller_lines2(c.pm, s);
+  same_miller_half(c.pm, nr, dl + r.iota, sl.d_fb.p, r_inc, dl + r.msg, sl.d_F.p, lane, s);
+  same_check_half(nr, sl.d_S.p, sl.d_F.p, sl.d_G.p, r_ok, lane, s);
+  launch_same_retry_results(dl, nr, r_inc, r_code, r_ok, c.sres, s);
+  HIPCHK(hipGetLastError());
+}
+// Aggregate phase: each group's sum over the sets that answered 1, from the signatures decoded once, in the aggregate
+// buffer `da` (hl::SameAgg `la`; the include bytes went up with the inputs).  Enqueued only.
+void same_aggregate_phase(const SameCall& c, const hl::SameAgg& la, const SameAggOut& agg, uint8_t* da,
+                          std::vector<uint8_t>& h_agg, std::vector<uint32_t>& h_cnt) {
+  hipStream_t s = c.br.s;
+  launch_same_agg(c.pb.sig_aff, c.n, c.sres, agg.include ? da + la.inc : nullptr, c.ab.group_first, c.G,
+                  reinterpret_cast<uint32_t*>(da + la.sums), reinterpret_cast<uint32_t*>(da + la.count), da + la.out,
+                  agg.out_sig_len, s);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(h_agg.data(), da + la.out, h_agg.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(h_cnt.data(), da + la.count, (size_t)c.G * 4, hipMemcpyDeviceToHost, s));
+}
+
+// What a same-message call brings back; it reaches the caller only on BLSGPU_OK
+struct SameHost {
+  std::vector<int8_t> set, grp;
+  std::vector<uint8_t> agg;
+  std::vector<uint32_t> cnt;
+  blsgpu_same_message_stats st;
+};
+// The device side of both same-message verification calls, under helper_call: the driver of the phases above.  It
+// shows what grows where, which host vectors live until the final synchronize, and when the Miller lines are built.
+int same_message_on_device(Device& d, Slot& sl, hipStream_t s, const Grouped& a, const uint8_t* msgs, uint64_t seed,
+                           uint32_t flags, const SameAggOut* agg, SameHost& h) {
+  const uint32_t n = a.n, G = a.G;
+  std::vector<uint64_t> words;
+  uint64_t hash_key = 0;
+  if (int e = same_begin(d, a, seed, words, hash_key)) return e;
+  // group g signs unique message gmsg[g].  These host vectors are copied from: they live until the final synchronize
+  std::vector<uint32_t> gmsg, iota((size_t)G + 1), listed, riota;
+  const std::vector<uint8_t> umsgs = unique_messages(msgs, G, sp::msg_key(hash_key), gmsg);
+  std::vector<uint8_t> h_blk, h_inc;  // (copied to)
+  sp::Retry rt;                       // (rt.sets, rt.msg)
+  for (uint32_t g = 0; g <= G; g++) iota[g] = g;
+  const uint32_t U = (uint32_t)(umsgs.size() / 32);
+  h.st.unique_messages = U;
+  drained_on_error(d, [&](bool& sized) {
+    const Branches br = branches(d, s, same_serial());
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool lane_g = sp::form(G, flags) != 0;
+    const uint32_t L = awr_lanes(G, n), lanes = awr_launch_lanes(G, L);
+    const hl::Same l(G, n, U, a.sig_stride, a.pk_bytes != nullptr, lanes);
+    // every buffer of the group phase grows here, while none of the three streams has work (each call ends with all
+    // of them synchronized); the retry phase grows only buffers the group phase does not use, after its synchronize
+    sl.d_in.ensure(l.in_total);
+    sl.d_bytes.ensure(l.bytes_total);
+    sl.d_work.ensure(l.work_words);
+    if (lane_g) sl.d_lines.ensure(l.lines_words);
+    // BLSGPU_SAME_BLOCK_CHECK: the block phase's buffers grow here too; the descent's, like the retry phase's, after
+    // the synchronize before it, and they are buffers no other phase uses
+    const uint32_t NB = sp::blocks(G, flags);
+    const hl::SameBlocks lb(NB, NB ? same_block_tree_width(G) : 0, 0);
+    if (NB) {
+      sl.d_msmW.ensure(lb.work_words);
+      sl.d_res.ensure(lb.bytes_total);
+    }
+    // the aggregate phase's buffer too: one no other phase of the call uses
+    const hl::SameAgg la(G, n, agg ? agg->out_sig_len : 0);
+    if (agg) sl.d_msmB.ensure(la.total_words);
+    sized = true;
+    SameCall c = same_upload(d, br, a, flags, l, L, lanes, words.data(), umsgs, gmsg.data(), iota.data());
+    uint8_t* da = agg ? reinterpret_cast<uint8_t*>(sl.d_msmB.p) : nullptr;
+    if (agg && agg->include && n) HIPCHK(hipMemcpyAsync(da + la.inc, agg->include, n, hipMemcpyHostToDevice, s));
+    same_group_items(c);
+    const bool have_lines = lane_g;  // the message branch builds the Miller lines only for a lane-form group phase
+    if (!NB) {
+      same_group_checks(c, h.grp.data());
+    } else {
+      h_blk.resize(2 * (size_t)NB), h_inc.resize(G);  // any | ok per block; include per group
+      same_block_phase(c, sl, lb, NB, h_blk.data(), h_blk.data() + NB, h_inc.data(), h.grp.data());
+      h.st.form |= sp::kFormBlocks;
+      listed = sp::descent_list(G, NB, h_blk.data(), h_blk.data() + NB, h_inc.data());
+      if (const uint32_t nl = (uint32_t)listed.size()) {
+        const hl::SameBlocks ld(NB, 0, nl);
+        sl.d_fkeep.ensure(ld.descent_words);
+        sl.d_fbflags.ensure(ld.d_ok_bytes);
+        same_descent(c, sl, ld, listed, h.grp.data());
+        h.st.form |= c.lane(nl) ? sp::kFormDescent | sp::kFormDescentLane : sp::kFormDescent;
+      }
+    }
+    if (lane_g) h.st.form |= sp::kFormGroupLane;
+    rt = sp::retry_list(a.group_first, G, h.grp.data(), gmsg.data());
+    const uint32_t nr = (uint32_t)rt.sets.size();
+    h.st.groups_accepted = rt.groups_accepted;
+    h.st.groups_retried = rt.groups_retried;
+    h.st.retry_sets = nr;
+    if (nr) {
+      // after a synchronize of all three streams, and buffers the earlier phases do not use -- but for d_lines, which
+      // grows only when the group phase left it unused
+      const bool lane_r = c.lane(nr);
+      const hl::SameRetry r(nr);
+      grow_retry_buffers(sl, r, lane_r);
+      if (lane_r && !have_lines) {
+        sl.d_lines.ensure(l.lines_words);
+        c.pm.lines = sl.d_lines.p;
+      }
+      riota.resize((size_t)nr + 1);
+      for (uint32_t q = 0; q <= nr; q++) riota[q] = q;
+      same_retry_phase(c, sl, r, rt, riota, lane_r && !have_lines);
+      if (lane_r) h.st.form |= sp::kFormRetryLane;
+    }
+    if (agg) same_aggregate_phase(c, la, *agg, da, h.agg, h.cnt);
+    if (n) HIPCHK(hipMemcpyAsync(h.set.data(), c.sres, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    h.st.device_ms = ms_since(t0);
+  });
+  return BLSGPU_OK;
+}
+
+// Both same-message verification calls.  agg null: blsgpu_verify_same_message, which launches what it always
+// launched.  Else the aggregate phase follows the retry phase.
+int verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first, const uint8_t* msgs,
+                        const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs, uint32_t sig_stride,
+                        const uint32_t* sig_len, uint64_t seed, uint32_t flags, int8_t* set_result,
+                        int8_t* group_result, blsgpu_same_message_stats* stats, const SameAggOut* agg) {
+  if (!ctx || ctx->devs.empty() || !group_first || !msgs || !sigs || !sig_len || !set_result) return BLSGPU_ERR_ARGS;
+  if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
+  if (sig_stride < 96 || (flags & ~(BLSGPU_SAME_LANE_FORMS | BLSGPU_SAME_BLOCK_CHECK))) return BLSGPU_ERR_ARGS;
+  if (agg && (agg->out_sig_len != 96 && agg->out_sig_len != 192)) return BLSGPU_ERR_ARGS;
+  if (agg && n_groups && (!agg->out_sig || !agg->count)) return BLSGPU_ERR_ARGS;
+  if (n_groups == 0) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    return BLSGPU_OK;
+  }
+  Grouped a{n_groups, group_first, sigs, sig_stride, sig_len, pk_bytes, pk_index};
+  if (int e = check_group_layout(a)) return e;
+  const uint32_t n = a.n, G = n_groups;
+  SameHost h;
+  h.set.resize(n), h.grp.resize(G), h.agg.resize(agg ? (size_t)G * agg->out_sig_len : 0), h.cnt.resize(agg ? G : 0);
+  memset(&h.st, 0, sizeof h.st);
+  const int rc = helper_call(ctx, true, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    return same_message_on_device(d, sl, s, a, msgs, seed, flags, agg, h);
+  });
+  if (rc == BLSGPU_OK) {  // results reach the caller only when every one of them was computed
+    if (n) memcpy(set_result, h.set.data(), n);
+    if (group_result) memcpy(group_result, h.grp.data(), G);
+    if (stats) *stats = h.st;
+    if (agg) {
+      memcpy(agg->out_sig, h.agg.data(), h.agg.size());
+      memcpy(agg->count, h.cnt.data(), (size_t)G * 4);
+    }
+  }
+  return rc;
+}
+
+// ---- batched AggregateVerify -----------------------------------------------------------------------------------
+// A job's signature is one more pair of the job, (-g1, sig): k pairs are k + 1 Miller items in the job's own
+// accumulators and one final exponentiation (aggverify_plan.hpp, k_aggverify.hip, DESIGN.md 4.5).
+// (its inputs AvArgs and where everything lies, AvCall, are helper_buffers.hpp.)
+// Copies the call's inputs and its plan to d_in (hl::AggVerify `l`)
+void av_upload(Slot& sl, const hl::AggVerify& l, const AvArgs& a, const avp::Plan& plan,
+               const std::vector<uint8_t>& umsgs, const uint32_t* pmsg, hipStream_t s) {
+  uint8_t* din = sl.d_in.p;
+  const uint32_t J = a.J, C = plan.n_chunks();
+  HIPCHK(hipMemcpyAsync(din + l.gf, a.job_first, (size_t)(J + 1) * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(din + l.len, a.sig_len, (size_t)J * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(din + l.sigs, a.sigs, (size_t)J * a.sig_stride, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(din + l.fr, plan.f_ranges.data(), (size_t)2 * J * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(din + l.cf, plan.chunk_first.data(), (size_t)(C + 1) * 4, hipMemcpyHostToDevice, s));
+  if (!plan.chunk_items.empty())
+    HIPCHK(hipMemcpyAsync(din + l.ci, plan.chunk_items.data(), plan.chunk_items.size() * 4, hipMemcpyHostToDevice, s));
+  if (a.n) {
+    HIPCHK(hipMemcpyAsync(din + l.keys, a.pk_bytes ? (const void*)a.pk_bytes : (const void*)a.pk_index, l.key_bytes,
+                          hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(din + l.umsg, umsgs.data(), umsgs.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(din + l.pmsg, pmsg, (size_t)a.n * 4, hipMemcpyHostToDevice, s));
+  }
+}
+// Three branches from the input copy, joined into s, then every job's signature item
+void av_items(Slot& sl, const Branches& br, const hl::AggVerify& l, const AvArgs& a, const AvCall& c, bool lane) {
+  three_branches(
+      br,
+      [&](hipStream_t s) {  // signatures: decode + subgroup check (cooperative for small calls)
+        launch_sig_decode(c.pb, a.J, s, a.J <= 4096, nullptr, false, true);
+      },
+      [&](hipStream_t sb) {  // keys: KeyValidate when they are untrusted, then every pair's affine point and code
+        if (a.validate())
+          launch_key_validate(sl.d_in.p + l.keys, a.n, a.pk_len, a.pk_len, sl.d_in.p + l.kv96,
+                              reinterpret_cast<int8_t*>(sl.d_bytes.p + l.b_kv), sb);
+        launch_av_pair_items(c.av, sb);
+      },
+      [&](hipStream_t sc) {  // messages: H(m) affine, and in the lane form the Miller lines of those columns
+        launch_msg_branch(c.pm, lane, sc);
+      });
+  launch_av_job_items(c.av, br.s);
+}
+// Accumulate, reduce to F_j, check and write the results to d_res (enqueued only)
+void av_check(Slot& sl, const hl::AggVerify& l, const avp::CallPlan& p, const AvCall& c, int8_t* d_res,
+              hipStream_t s) {
+  const uint32_t J = c.av.n_jobs, U = c.av.n_umsg;
+  uint32_t* F = sl.d_work.p + l.w_F;
+  uint8_t* d_ok = sl.d_bytes.p + l.b_ok;
+  const uint32_t* d_fr = reinterpret_cast<uint32_t*>(sl.d_in.p + l.fr);
+  if (!p.lane) {
+    launch_miller_coop(c.px, false, s, false);
+  } else {
+    // the signature columns' lines: columns U .. M - 1, addressed as a call of J columns in the same arrays
+    PipelineBuffers ps = c.pm;
+    ps.n_umsg = J;
+    ps.h_aff = c.pm.h_aff + U;
+    ps.mflags = c.pm.mflags + U;
+    ps.lines = c.pm.lines + U;
+    launch_miller_lines2(ps, s);
+    launch_miller_acc(c.px, false, s);
+  }
+  if (p.lane_reduce)
+    launch_av_reduce_lane(c.px.f_chunk, c.px.n, d_fr, J, F, s);
+  else
+    launch_group_reduce(c.px, d_fr, J, F, s);
+  launch_av_check(F, J, c.av.checked, d_ok, p.lane, s);
+  launch_av_results(J, c.av.job_code, c.av.checked, d_ok, d_res, s);
+  HIPCHK(hipGetLastError());
 }
 
 }  // namespace
@@ -265,348 +741,9 @@ int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const u
 
 uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets) { return awr_lanes(n_groups, n_sets); }
 
-// ---- one-call same-message verification ------------------------------------------------------------------------
-// A phase of at most kSameCoopMax pairings takes the cooperative kernels (a workgroup per Miller loop and per check:
-// latency), a larger one the lane forms (throughput).  512 is the coop_max option's default, taken as a constant: the
-// helper calls read no option.
-constexpr uint32_t kSameCoopMax = 512;
-uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags) {
-  return (flags & BLSGPU_SAME_LANE_FORMS) || n_items > kSameCoopMax ? 1u : 0u;
-}
-// BLSGPU_SAME_BLOCK_CHECK: groups per block, the group_sets option's default as a constant (as kSameCoopMax above)
-static_assert(SAME_BLOCK_GROUPS == 1024, "include/blsgpu.h documents blocks of 1024 groups");
-uint32_t blsgpu_same_message_blocks(uint32_t n_groups, uint32_t flags) {
-  return flags & BLSGPU_SAME_BLOCK_CHECK ? n_groups / SAME_BLOCK_GROUPS + (n_groups % SAME_BLOCK_GROUPS ? 1u : 0u) : 0u;
-}
-namespace {
-// diagnostics (tools/bench_same_message.py): the three branches of the group phase on one stream
-inline bool same_serial() {
-  static const bool on = [] {
-    const char* v = getenv("BLSGPU_SAME_SERIAL");
-    return v && v[0] == '1';
-  }();
-  return on;
-}
-// Miller values and checks of one phase, in two halves.  Miller half: item i < n_items pairs pk_aff[i] (W_G1A, stride
-// n_items) with H(msg_idx[i]) when include[i], F_i (W_FP12, stride n_items).  iota = 0, 1, .., n_items: one item per
-// Miller chunk.  Check half: ok[i] = FinalExp(F_i * MillerLoop(-g1, S_i)) == 1 with S (W_G2J, stride n_items).
-// Cooperative form: k_miller_coop, and k_group_check with its own Miller loop.  Lane form: the messages' stored lines
-// (pm.lines), k_miller_acc6 (six lanes per pairing), MillerLoop(-g1, S) on one lane per item (into Gs) and the final
-// exponentiation on six (k_group_check6).
-void same_miller_half(const PipelineBuffers& pm, uint32_t n_items, const uint32_t* iota, uint32_t* pk_aff,
-                      uint8_t* include, const uint32_t* msg_idx, uint32_t* F, bool lane, hipStream_t s) {
-  PipelineBuffers pb = pm;
-  pb.n = n_items;
-  pb.pk_aff = pk_aff;
-  pb.include = include;
-  pb.msg_idx = msg_idx;
-  pb.n_chunks = n_items;
-  pb.chunk_first = iota;
-  pb.chunk_items = iota;
-  pb.f_chunk = F;
-  if (!lane)
-    launch_miller_coop(pb, false, s, false);
-  else
-    launch_miller_acc6(pb, false, s);
-}
-void same_check_half(uint32_t n_items, const uint32_t* S, const uint32_t* F, uint32_t* Gs, uint8_t* ok, bool lane,
-                     hipStream_t s) {
-  if (!lane) {
-    launch_group_check(S, F, n_items, ok, s);
-  } else {
-    launch_group_sig_miller(S, n_items, Gs, s, false, true);
-    launch_group_check6(F, Gs, n_items, ok, s);
-  }
-}
-void same_pairing_phase(const PipelineBuffers& pm, uint32_t n_items, const uint32_t* iota, uint32_t* pk_aff,
-                        uint8_t* include, const uint32_t* msg_idx, const uint32_t* S, uint32_t* F, uint32_t* Gs,
-                        uint8_t* ok, bool lane, hipStream_t s) {
-  same_miller_half(pm, n_items, iota, pk_aff, include, msg_idx, F, lane, s);
-  same_check_half(n_items, S, F, Gs, ok, lane, s);
-}
-// The aggregate outputs of blsgpu_verify_same_message_agg; blsgpu_verify_same_message has none.
-struct SameAggOut {
-  const uint8_t* include;  // [n_sets], nullable
-  uint8_t* out_sig;
-  uint32_t out_sig_len;
-  uint32_t* count;
-};
-
-// The body of both same-message verification calls.  agg null: blsgpu_verify_same_message, which launches what it
-// always launched.  Else the aggregate phase follows the retry phase.
-int verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first, const uint8_t* msgs,
-                        const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs, uint32_t sig_stride,
-                        const uint32_t* sig_len, uint64_t seed, uint32_t flags, int8_t* set_result,
-                        int8_t* group_result, blsgpu_same_message_stats* stats, const SameAggOut* agg) {
-  if (!ctx || ctx->devs.empty() || !group_first || !msgs || !sigs || !sig_len || !set_result) return BLSGPU_ERR_ARGS;
-  if ((pk_bytes != nullptr) == (pk_index != nullptr)) return BLSGPU_ERR_ARGS;
-  if (sig_stride < 96 || (flags & ~(BLSGPU_SAME_LANE_FORMS | BLSGPU_SAME_BLOCK_CHECK))) return BLSGPU_ERR_ARGS;
-  if (agg && (agg->out_sig_len != 96 && agg->out_sig_len != 192)) return BLSGPU_ERR_ARGS;
-  if (agg && n_groups && (!agg->out_sig || !agg->count)) return BLSGPU_ERR_ARGS;
-  if (n_groups == 0) {
-    if (stats) memset(stats, 0, sizeof *stats);
-    return BLSGPU_OK;
-  }
-  Grouped a{n_groups, group_first, sigs, sig_stride, sig_len, pk_bytes, pk_index};
-  if (int e = check_group_layout(a)) return e;
-  const uint32_t n = a.n, G = n_groups;
-  std::vector<int8_t> h_set(n), h_grp(G);
-  std::vector<uint8_t> h_agg(agg ? (size_t)G * agg->out_sig_len : 0);
-  std::vector<uint32_t> h_cnt(agg ? G : 0);
-  blsgpu_same_message_stats st;
-  memset(&st, 0, sizeof st);
-  const int rc = helper_call(ctx, true, [&](Device& d, Slot& sl, hipStream_t s) -> int {
-    std::vector<uint64_t> words;
-    uint64_t hash_key = 0;
-    if (int e = same_begin(d, a, seed, words, hash_key)) return e;
-    // messages, deduplicated as plan_run does (run_plan.hpp): group g signs unique message gmsg[g]
-    std::vector<uint32_t> gmsg(G), uniq;
-    {
-      MsgIndex mi(G, hash_key ^ 0x6a09e667f3bcc908ull);
-      for (uint32_t g = 0; g < G; g++) gmsg[g] = mi.find_or_add(msgs, g, uniq);
-    }
-    const uint32_t U = (uint32_t)uniq.size();
-    st.unique_messages = U;
-    bool streams_used = false;
-    try {
-      if (!d.same_st[0]) {
-        for (auto& e : d.same_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIPCHK(hipStreamCreateWithFlags(&d.same_st[1], hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&d.same_st[0], hipStreamNonBlocking));
-      }
-      const auto t0 = std::chrono::steady_clock::now();
-      const bool serial = same_serial();
-      hipStream_t sb = serial ? s : d.same_st[0], sc = serial ? s : d.same_st[1];
-      const bool lane_g = blsgpu_same_message_form(G, flags) != 0;
-      const uint32_t L = awr_lanes(G, n), lanes = awr_launch_lanes(G, L);
-      const hl::Same l(G, n, U, sig_stride, pk_bytes != nullptr, lanes);
-      // every buffer of the group phase grows here, while none of the three streams has work (each call ends with all
-      // of them synchronized); the retry phase grows only buffers the group phase does not use, after its synchronize
-      sl.d_in.ensure(l.in_total);
-      sl.d_bytes.ensure(l.bytes_total);
-      sl.d_work.ensure(l.work_words);
-      if (lane_g) sl.d_lines.ensure(l.lines_words);
-      // BLSGPU_SAME_BLOCK_CHECK: the block phase's buffers grow here too; the descent's, like the retry phase's, after
-      // the synchronize before it, and they are buffers no other phase uses
-      const uint32_t NB = blsgpu_same_message_blocks(G, flags);
-      const hl::SameBlocks lb(NB, NB ? same_block_tree_width(G) : 0, 0);
-      if (NB) {
-        sl.d_msmW.ensure(lb.work_words);
-        sl.d_res.ensure(lb.bytes_total);
-      }
-      // the aggregate phase's buffer too: one no other phase of the call uses
-      const hl::SameAgg la(G, n, agg ? agg->out_sig_len : 0);
-      if (agg) sl.d_msmB.ensure(la.total_words);
-      streams_used = true;
-      uint8_t* din = sl.d_in.p;
-      uint8_t* db = sl.d_bytes.p;
-      uint32_t* w = sl.d_work.p;
-      std::vector<uint32_t> iota((size_t)G + 1);
-      for (uint32_t g = 0; g <= G; g++) iota[g] = g;
-      std::vector<uint8_t> umsgs((size_t)U * 32);
-      for (uint32_t u = 0; u < U; u++) memcpy(umsgs.data() + (size_t)u * 32, msgs + (size_t)uniq[u] * 32, 32);
-      PipelineBuffers pb;  // the signature decode
-      const AwrBuffers ab = same_inputs(d, a, l, db, words.data(), lanes, s, pb);
-      HIPCHK(hipMemcpyAsync(din + l.umsg, umsgs.data(), (size_t)U * 32, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + l.gmsg, gmsg.data(), (size_t)G * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + l.iota, iota.data(), (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
-      uint8_t* da = agg ? reinterpret_cast<uint8_t*>(sl.d_msmB.p) : nullptr;
-      if (agg && agg->include && n) HIPCHK(hipMemcpyAsync(da + la.inc, agg->include, n, hipMemcpyHostToDevice, s));
-      AwrBuffers ab_pk = ab;  // the G1 sum runs beside the G2 sum: its own window scratch
-      ab_pk.tab = w + l.w_tab_pk;
-      uint32_t* g_pk_aff = w + l.w_pk_aff;
-      uint32_t* g_inv = w + l.w_inv;
-      uint32_t* g_F = w + l.w_F;
-      uint32_t* g_G = w + l.w_G;
-      PipelineBuffers pm{};  // the message branch
-      pm.umsgs = din + l.umsg;
-      pm.n_umsg = U;
-      pm.nm = U;
-      pm.inv_buf = w + l.w_minv;
-      pm.h_aff = w + l.w_haff;
-      pm.h_jac = w + l.w_hjac;
-      pm.h_norm = w + l.w_hnorm;
-      pm.h_prep = w + l.w_hprep;
-      pm.h_q = w + l.w_hq;
-      pm.mflags = db + l.b_mf;
-      pm.lines = sl.d_lines.p;
-      uint8_t* g_inc = db + l.b_inc;
-      int8_t* g_code = reinterpret_cast<int8_t*>(db + l.b_code);
-      uint8_t* g_ok = db + l.b_ok;
-      int8_t* d_gres = reinterpret_cast<int8_t*>(db + l.b_gres);
-      int8_t* d_sres = reinterpret_cast<int8_t*>(db + l.b_sres);
-      const uint32_t* d_gmsg = reinterpret_cast<uint32_t*>(din + l.gmsg);
-      const uint32_t* d_iota = reinterpret_cast<uint32_t*>(din + l.iota);
-      // ---- group phase: three branches from the input copy, joined into s
-      HIPCHK(hipEventRecord(d.same_ev[0], s));
-      if (!serial) {
-        HIPCHK(hipStreamWaitEvent(sb, d.same_ev[0], 0));
-        HIPCHK(hipStreamWaitEvent(sc, d.same_ev[0], 0));
-      }
-      // (a) signatures: decode + subgroup check (cooperative for small calls, as small verification runs), S_g
-      launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, true);
-      launch_awr_sum_sig(ab, L, s);
-      // (b) keys: P_g and the batch inverses of its z
-      launch_awr_sum_pk(ab_pk, L, sb);
-      launch_batch_inv(ab.sum_pk, G, 2 * W_FP, g_inv, G, sb);
-      HIPCHK(hipEventRecord(d.same_ev[1], sb));
-      // (c) messages: H(m) affine, and in the lane form its Miller lines
-      bool have_lines = false;
-      launch_hash_to_g2(pm, sc, U <= 4096, false);
-      launch_h_affine(pm, sc);
-      if (lane_g) {
-        launch_miller_lines2(pm, sc);
-        have_lines = true;
-      }
-      HIPCHK(hipEventRecord(d.same_ev[2], sc));
-      if (!serial) {
-        HIPCHK(hipStreamWaitEvent(s, d.same_ev[1], 0));
-        HIPCHK(hipStreamWaitEvent(s, d.same_ev[2], 0));
-      }
-      launch_same_group_items(ab, g_inv, g_pk_aff, g_inc, g_code, s);
-      std::vector<uint32_t> listed;  // (alive until the final synchronize: it is copied from)
-      if (!NB) {
-        same_pairing_phase(pm, G, d_iota, g_pk_aff, g_inc, d_gmsg, ab.sum_sig, g_F, g_G, g_ok, lane_g, s);
-        launch_same_group_results(ab.group_first, G, n, g_inc, g_code, g_ok, d_sres, d_gres, s);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h_grp.data(), d_gres, G, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
-      } else {
-        // ---- block phase: F_b, S_b per block of groups and one check per block.  S_b needs the sums
-        // and the include flags only: it runs on sb, beside the Miller loops, and is joined into s before the check.
-        const bool lane_b = blsgpu_same_message_form(NB, flags) != 0;
-        uint32_t* bw = sl.d_msmW.p;
-        uint32_t* b_F = bw + lb.w_F;
-        uint32_t* b_S = bw + lb.w_S;
-        uint8_t* b_any = sl.d_res.p + lb.b_any;
-        uint8_t* b_ok = sl.d_res.p + lb.b_ok;
-        HIPCHK(hipEventRecord(d.same_ev[0], s));
-        if (!serial) HIPCHK(hipStreamWaitEvent(sb, d.same_ev[0], 0));
-        launch_same_block_sum(ab.sum_sig, g_inc, G, NB, b_S, b_any, sb);
-        HIPCHK(hipEventRecord(d.same_ev[1], sb));
-        same_miller_half(pm, G, d_iota, g_pk_aff, g_inc, d_gmsg, g_F, lane_g, s);
-        launch_same_block_prod(g_F, g_inc, G, NB, bw + lb.w_T0, bw + lb.w_T1, b_F, s);
-        if (!serial) HIPCHK(hipStreamWaitEvent(s, d.same_ev[1], 0));
-        same_check_half(NB, b_S, b_F, sl.d_msmW.p + lb.w_G, b_ok, lane_b, s);
-        launch_same_block_results(ab.group_first, G, n, g_inc, g_code, b_any, b_ok, d_sres, d_gres, s);
-        HIPCHK(hipGetLastError());
-        std::vector<uint8_t> h_blk(2 * (size_t)NB), h_inc(G);
-        HIPCHK(hipMemcpyAsync(h_blk.data(), b_any, NB, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_blk.data() + NB, b_ok, NB, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_inc.data(), g_inc, G, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_grp.data(), d_gres, G, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
-        st.form |= 4;
-        // ---- descent: the included groups of the failed blocks, each checked from its own F_g, S_g.  A failed block
-        // with one included group has its answer already: that group failed.
-        for (uint32_t b = 0; b < NB; b++) {
-          if (!h_blk[b] || h_blk[NB + b]) continue;
-          const uint32_t first = b * SAME_BLOCK_GROUPS, last = std::min<uint64_t>(G, (uint64_t)first + SAME_BLOCK_GROUPS);
-          const size_t before = listed.size();
-          for (uint32_t g = first; g < last; g++)
-            if (h_inc[g]) listed.push_back(g);
-          if (listed.size() - before == 1) listed.pop_back();
-        }
-        const uint32_t nl = (uint32_t)listed.size();
-        if (nl) {
-          const bool lane_d = blsgpu_same_message_form(nl, flags) != 0;
-          const hl::SameBlocks ld(NB, 0, nl);
-          sl.d_fkeep.ensure(ld.descent_words);
-          sl.d_fbflags.ensure(ld.d_ok_bytes);
-          uint32_t* dw = sl.d_fkeep.p;
-          uint8_t* l_ok = sl.d_fbflags.p;
-          HIPCHK(hipMemcpyAsync(dw + ld.d_list, listed.data(), (size_t)nl * 4, hipMemcpyHostToDevice, s));
-          launch_same_gather(g_F, ab.sum_sig, G, dw + ld.d_list, nl, dw + ld.d_F, dw + ld.d_S, s);
-          same_check_half(nl, dw + ld.d_S, dw + ld.d_F, dw + ld.d_G, l_ok, lane_d, s);
-          launch_same_descent_results(ab.group_first, G, n, dw + ld.d_list, nl, l_ok, d_sres, d_gres, s);
-          HIPCHK(hipGetLastError());
-          HIPCHK(hipMemcpyAsync(h_grp.data(), d_gres, G, hipMemcpyDeviceToHost, s));
-          HIPCHK(hipStreamSynchronize(s));
-          st.form |= lane_d ? 8 | 16 : 8;
-        }
-      }
-      if (lane_g) st.form |= 1;
-      // ---- retry phase: every set of a non-empty group whose check did not hold, on its own with r = 1
-      std::vector<uint32_t> rlist, rmsg, riota;  // (alive until the final synchronize: they are copied from)
-      for (uint32_t g = 0; g < G; g++) {
-        if (group_first[g + 1] == group_first[g]) continue;
-        if (h_grp[g] == 1) {
-          st.groups_accepted++;
-          continue;
-        }
-        st.groups_retried++;
-        for (uint32_t k = group_first[g]; k < group_first[g + 1]; k++) {
-          rlist.push_back(k);
-          rmsg.push_back(gmsg[g]);
-        }
-      }
-      const uint32_t nr = (uint32_t)rlist.size();
-      st.retry_sets = nr;
-      if (nr) {
-        const bool lane_r = blsgpu_same_message_form(nr, flags) != 0;
-        const hl::SameRetry r(nr);
-        sl.d_list.ensure(r.list_words);
-        sl.d_ok.ensure(r.ok_bytes);
-        sl.d_fb.ensure(r.fb_words);
-        sl.d_S.ensure(r.S_words);
-        sl.d_F.ensure(r.F_words);
-        if (lane_r) sl.d_G.ensure(r.F_words);
-        if (lane_r && !have_lines) {
-          sl.d_lines.ensure(l.lines_words);
-          pm.lines = sl.d_lines.p;
-        }
-        riota.resize((size_t)nr + 1);
-        for (uint32_t q = 0; q <= nr; q++) riota[q] = q;
-        uint32_t* dl = sl.d_list.p;
-        HIPCHK(hipMemcpyAsync(dl, rlist.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dl + r.msg, rmsg.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(dl + r.iota, riota.data(), (size_t)(nr + 1) * 4, hipMemcpyHostToDevice, s));
-        uint8_t* r_inc = sl.d_ok.p;
-        int8_t* r_code = reinterpret_cast<int8_t*>(sl.d_ok.p + r.code);
-        uint8_t* r_ok = sl.d_ok.p + r.ok;
-        launch_same_retry_items(ab, dl, nr, sl.d_fb.p, sl.d_S.p, r_inc, r_code, s);
-        if (lane_r && !have_lines) launch_miller_lines2(pm, s);
-        same_pairing_phase(pm, nr, dl + r.iota, sl.d_fb.p, r_inc, dl + r.msg, sl.d_S.p, sl.d_F.p, sl.d_G.p, r_ok, lane_r,
-                           s);
-        launch_same_retry_results(dl, nr, r_inc, r_code, r_ok, d_sres, s);
-        HIPCHK(hipGetLastError());
-        if (lane_r) st.form |= 2;
-      }
-      // ---- aggregate phase: each group's sum over the sets that answered 1, from the signatures decoded once
-      if (agg) {
-        launch_same_agg(pb.sig_aff, n, d_sres, agg->include ? da + la.inc : nullptr, ab.group_first, G,
-                        reinterpret_cast<uint32_t*>(da + la.sums), reinterpret_cast<uint32_t*>(da + la.count),
-                        da + la.out, agg->out_sig_len, s);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(h_agg.data(), da + la.out, h_agg.size(), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_cnt.data(), da + la.count, (size_t)G * 4, hipMemcpyDeviceToHost, s));
-      }
-      if (n) HIPCHK(hipMemcpyAsync(h_set.data(), d_sres, n, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      st.device_ms = ms_since(t0);
-    } catch (HipError&) {
-      // no branch may outlive the call: the next helper call reuses, and may grow, the buffers they work on
-      if (streams_used) {
-        (void)hipStreamSynchronize(d.table_stream);
-        for (hipStream_t x : d.same_st)
-          if (x) (void)hipStreamSynchronize(x);
-      }
-      throw;
-    }
-    return BLSGPU_OK;
-  });
-  if (rc == BLSGPU_OK) {  // results reach the caller only when every one of them was computed
-    if (n) memcpy(set_result, h_set.data(), n);
-    if (group_result) memcpy(group_result, h_grp.data(), G);
-    if (stats) *stats = st;
-    if (agg) {
-      memcpy(agg->out_sig, h_agg.data(), h_agg.size());
-      memcpy(agg->count, h_cnt.data(), (size_t)G * 4);
-    }
-  }
-  return rc;
-}
-}  // namespace
+// ---- one-call same-message verification: the rules are same_plan.hpp, the phases and their driver are above
+uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags) { return sp::form(n_items, flags); }
+uint32_t blsgpu_same_message_blocks(uint32_t n_groups, uint32_t flags) { return sp::blocks(n_groups, flags); }
 
 int blsgpu_verify_same_message(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first, const uint8_t* msgs,
                                const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
@@ -629,9 +766,7 @@ int blsgpu_verify_same_message_agg(blsgpu_ctx* ctx, uint32_t n_groups, const uin
 
 uint32_t blsgpu_same_message_agg_lanes(uint32_t n_groups, uint32_t n_sets) { return sig_agg_lanes(n_groups, n_sets); }
 
-// ---- batched AggregateVerify -----------------------------------------------------------------------------------
-// A job's signature is one more pair of the job, (-g1, sig): k pairs are k + 1 Miller items in the job's own
-// accumulators and one final exponentiation (aggverify_plan.hpp, k_aggverify.hip, DESIGN.md 4.5).
+// ---- batched AggregateVerify: argument checks, plan, buffers, three branches, checks, stats
 uint32_t blsgpu_aggregate_verify_form(uint32_t n_items, uint32_t flags) {
   return avp::form(n_items, (flags & BLSGPU_AV_LANE_FORMS) != 0);
 }
@@ -649,14 +784,11 @@ int blsgpu_aggregate_verify(blsgpu_ctx* ctx, uint32_t n_jobs, const uint32_t* jo
     if (stats) memset(stats, 0, sizeof *stats);
     return BLSGPU_OK;
   }
-  if (n_jobs > (1u << 20) || job_first[0] != 0) return BLSGPU_ERR_ARGS;
-  for (uint32_t j = 0; j < n_jobs; j++)
-    if (job_first[j + 1] < job_first[j]) return BLSGPU_ERR_ARGS;
-  const uint32_t J = n_jobs, n = job_first[J];
-  if (n > (1u << 20)) return BLSGPU_ERR_ARGS;
-  if (sig_stride < 192)
-    for (uint32_t j = 0; j < J; j++)
-      if (sig_len[j] == 192) return BLSGPU_ERR_ARGS;
+  if (n_jobs > (1u << 20)) return BLSGPU_ERR_ARGS;  // (before job_first is read)
+  AvArgs a{n_jobs, 0, job_first, pk_bytes, pk_len, pk_index, sigs, sig_stride, sig_len, flags};
+  if (int e = check_offsets(job_first, n_jobs, a.n)) return e;
+  if (int e = check_sig_lens(sig_len, n_jobs, sig_stride)) return e;
+  const uint32_t J = n_jobs, n = a.n;
   std::vector<int8_t> h_res(J);
   std::vector<uint32_t> h_fb(J);
   std::vector<uint8_t> h_chk(J);
@@ -666,172 +798,36 @@ int blsgpu_aggregate_verify(blsgpu_ctx* ctx, uint32_t n_jobs, const uint32_t* jo
     if (pk_index)
       for (uint32_t k = 0; k < n; k++)
         if (pk_index[k] >= d.table_n) return BLSGPU_ERR_ARGS;
-    // messages, deduplicated over the whole call: pair k signs unique message pmsg[k].  The call draws no randomness,
-    // so the index is keyed by a constant (the key only spreads the table's probes; equality is by memcmp).
-    std::vector<uint32_t> pmsg(n), uniq;
-    {
-      MsgIndex mi(n, 0xbb67ae8584caa73bull);
-      for (uint32_t k = 0; k < n; k++) pmsg[k] = mi.find_or_add(msgs, k, uniq);
-    }
-    const uint32_t U = (uint32_t)uniq.size();
-    // every non-empty job is planned: which of them the device rejects is known only after the decodes, and their
-    // items are switched off by the include bytes (one synchronize less than reading the status back first)
-    const avp::Counts planned = avp::count(job_first, J, nullptr, 1);
-    const bool lane = blsgpu_aggregate_verify_form(planned.items, flags) != 0;
-    const uint32_t kc = avp::chunk_items_for(job_first, J, lane ? 1 : 0, (flags & BLSGPU_AV_LANE_FORMS) != 0);
-    const avp::Plan plan = avp::build(job_first, J, nullptr, kc);
-    const uint32_t C = plan.n_chunks();
-    // jobs of few chunks: a lane per job multiplies its chunk values; else a wave per job
-    const bool lane_reduce = lane && (uint64_t)C <= (uint64_t)avp::kLaneReduceMax * planned.jobs;
+    // messages, deduplicated over the whole call: pair k signs unique message pmsg[k]
+    std::vector<uint32_t> pmsg;
+    const std::vector<uint8_t> umsgs = unique_messages(msgs, n, avp::kMsgKey, pmsg);
+    const uint32_t U = (uint32_t)(umsgs.size() / 32);
+    const avp::CallPlan p = avp::plan_call(job_first, J, a.lane_flag());
     st.pairs = n;
     st.unique_messages = U;
-    st.form = lane ? 1 : 0;
-    bool streams_used = false;
-    try {
-      if (!d.same_st[0]) {
-        for (auto& e : d.same_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIPCHK(hipStreamCreateWithFlags(&d.same_st[1], hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&d.same_st[0], hipStreamNonBlocking));
-      }
+    st.form = p.lane ? 1 : 0;
+    drained_on_error(d, [&](bool& sized) {
+      const Branches br = branches(d, s, false);
       const auto t0 = std::chrono::steady_clock::now();
-      hipStream_t sb = d.same_st[0], sc = d.same_st[1];
-      const hl::AggVerify l(J, n, U, C, sig_stride, pk_bytes != nullptr, pk_len, validate);
+      const hl::AggVerify l(J, n, U, p.n_chunks, sig_stride, pk_bytes != nullptr, pk_len, validate);
       // every buffer grows here, while none of the three streams has work (each call ends with all of them synchronized)
       sl.d_in.ensure(l.in_total);
       sl.d_bytes.ensure(l.bytes_total);
       sl.d_work.ensure(l.work_words);
-      if (lane) sl.d_lines.ensure(l.lines_words);
-      streams_used = true;
-      uint8_t* din = sl.d_in.p;
-      uint8_t* db = sl.d_bytes.p;
-      uint32_t* w = sl.d_work.p;
-      std::vector<uint8_t> umsgs((size_t)U * 32);
-      for (uint32_t u = 0; u < U; u++) memcpy(umsgs.data() + (size_t)u * 32, msgs + (size_t)uniq[u] * 32, 32);
-      HIPCHK(hipMemcpyAsync(din + l.gf, job_first, (size_t)(J + 1) * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + l.len, sig_len, (size_t)J * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + l.sigs, sigs, (size_t)J * sig_stride, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + l.fr, plan.f_ranges.data(), (size_t)2 * J * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(din + l.cf, plan.chunk_first.data(), (size_t)(C + 1) * 4, hipMemcpyHostToDevice, s));
-      if (!plan.chunk_items.empty())
-        HIPCHK(hipMemcpyAsync(din + l.ci, plan.chunk_items.data(), plan.chunk_items.size() * 4, hipMemcpyHostToDevice, s));
-      if (n) {
-        HIPCHK(hipMemcpyAsync(din + l.keys, pk_bytes ? (const void*)pk_bytes : (const void*)pk_index, l.key_bytes,
-                              hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(din + l.umsg, umsgs.data(), (size_t)U * 32, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(din + l.pmsg, pmsg.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-      }
-      PipelineBuffers pb{};  // the signature decode: one signature per job
-      pb.n = J;
-      pb.sigs = din + l.sigs;
-      pb.sig_len = reinterpret_cast<uint32_t*>(din + l.len);
-      pb.sig_stride = sig_stride;
-      pb.sig_aff = w;
-      pb.flags = db + l.b_fl;
-      pb.status = reinterpret_cast<int8_t*>(db + l.b_st);
-      PipelineBuffers pm{};  // the message branch: U hashed columns of the M = U + J
-      pm.umsgs = din + l.umsg;
-      pm.n_umsg = U;
-      pm.nm = (uint32_t)l.M;
-      pm.inv_buf = w + l.w_minv;
-      pm.h_aff = w + l.w_haff;
-      pm.h_jac = w + l.w_hjac;
-      pm.h_norm = w + l.w_hnorm;
-      pm.h_prep = w + l.w_hprep;
-      pm.h_q = w + l.w_hq;
-      pm.mflags = db + l.b_mf;
-      pm.lines = sl.d_lines.p;
-      AvBuffers av{};
-      av.n_pairs = n;
-      av.n_jobs = J;
-      av.n_items = (uint32_t)l.T;
-      av.n_umsg = U;
-      av.nm = (uint32_t)l.M;
-      av.job_first = reinterpret_cast<uint32_t*>(din + l.gf);
-      av.pk_bytes = !pk_bytes ? nullptr : validate ? din + l.kv96 : din + l.keys;
-      av.kv_status = validate ? reinterpret_cast<int8_t*>(db + l.b_kv) : nullptr;
-      av.pk_index = pk_bytes ? nullptr : reinterpret_cast<uint32_t*>(din + l.keys);
-      av.pk_table = d.table.p;
-      av.pk_table_n = d.table_n;
-      av.pair_msg = reinterpret_cast<uint32_t*>(din + l.pmsg);
-      av.sig_aff = pb.sig_aff;
-      av.sig_flags = pb.flags;
-      av.sig_status = pb.status;
-      av.pk_aff = w + l.w_pk_aff;
-      av.msg_idx = w + l.w_midx;
-      av.include = db + l.b_inc;
-      av.pair_code = reinterpret_cast<int8_t*>(db + l.b_code);
-      av.h_aff = pm.h_aff;
-      av.mflags = pm.mflags;
-      av.checked = db + l.b_chk;
-      av.job_code = reinterpret_cast<int8_t*>(db + l.b_jcode);
-      av.first_bad = reinterpret_cast<uint32_t*>(db + l.b_fb);
-      uint32_t* F = w + l.w_F;
-      uint8_t* d_ok = db + l.b_ok;
-      int8_t* d_res = reinterpret_cast<int8_t*>(db + l.b_res);
-      // ---- three branches from the input copy, joined into s
-      HIPCHK(hipEventRecord(d.same_ev[0], s));
-      HIPCHK(hipStreamWaitEvent(sb, d.same_ev[0], 0));
-      HIPCHK(hipStreamWaitEvent(sc, d.same_ev[0], 0));
-      // (a) signatures: decode + subgroup check (cooperative for small calls, as small verification runs)
-      launch_sig_decode(pb, J, s, J <= 4096, nullptr, false, true);
-      // (b) keys: KeyValidate when they are untrusted, then every pair's affine point and code
-      if (validate)
-        launch_key_validate(din + l.keys, n, pk_len, pk_len, din + l.kv96, reinterpret_cast<int8_t*>(db + l.b_kv), sb);
-      launch_av_pair_items(av, sb);
-      HIPCHK(hipEventRecord(d.same_ev[1], sb));
-      // (c) messages: H(m) affine, and in the lane form the Miller lines of those columns
-      launch_hash_to_g2(pm, sc, U <= 4096, false);
-      launch_h_affine(pm, sc);
-      if (lane) launch_miller_lines2(pm, sc);
-      HIPCHK(hipEventRecord(d.same_ev[2], sc));
-      HIPCHK(hipStreamWaitEvent(s, d.same_ev[1], 0));
-      HIPCHK(hipStreamWaitEvent(s, d.same_ev[2], 0));
-      launch_av_job_items(av, s);
-      PipelineBuffers px = pm;  // the Miller accumulation over the T items and the M columns
-      px.n = (uint32_t)l.T;
-      px.n_umsg = (uint32_t)l.M;
-      px.pk_aff = av.pk_aff;
-      px.include = av.include;
-      px.msg_idx = av.msg_idx;
-      px.n_chunks = C;
-      px.chunk_first = reinterpret_cast<uint32_t*>(din + l.cf);
-      px.chunk_items = reinterpret_cast<uint32_t*>(din + l.ci);
-      px.f_chunk = w + l.w_fchunk;
-      const uint32_t* d_fr = reinterpret_cast<uint32_t*>(din + l.fr);
-      if (!lane) {
-        launch_miller_coop(px, false, s, false);
-      } else {
-        // the signature columns' lines: columns U .. M - 1, addressed as a call of J columns in the same arrays
-        PipelineBuffers ps = pm;
-        ps.n_umsg = J;
-        ps.h_aff = pm.h_aff + U;
-        ps.mflags = pm.mflags + U;
-        ps.lines = pm.lines + U;
-        launch_miller_lines2(ps, s);
-        launch_miller_acc(px, false, s);
-      }
-      if (lane_reduce)
-        launch_av_reduce_lane(px.f_chunk, px.n, d_fr, J, F, s);
-      else
-        launch_group_reduce(px, d_fr, J, F, s);
-      launch_av_check(F, J, av.checked, d_ok, lane, s);
-      launch_av_results(J, av.job_code, av.checked, d_ok, d_res, s);
-      HIPCHK(hipGetLastError());
+      if (p.lane) sl.d_lines.ensure(l.lines_words);
+      sized = true;
+      av_upload(sl, l, a, p.plan, umsgs, pmsg.data(), s);
+      const AvCall c = av_buffers(d, l, a, U, p.n_chunks);
+      int8_t* d_res = reinterpret_cast<int8_t*>(sl.d_bytes.p + l.b_res);
+      av_items(sl, br, l, a, c, p.lane);
+      av_check(sl, l, p, c, d_res, s);
       HIPCHK(hipMemcpyAsync(h_res.data(), d_res, J, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(h_fb.data(), av.first_bad, (size_t)J * 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(h_chk.data(), av.checked, J, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(h_fb.data(), c.av.first_bad, (size_t)J * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(h_chk.data(), c.av.checked, J, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));  // every branch was joined into s: all three streams are idle
       st.device_ms = ms_since(t0);
-    } catch (HipError&) {
-      // no branch may outlive the call: the next helper call reuses, and may grow, the buffers they work on
-      if (streams_used) {
-        (void)hipStreamSynchronize(d.table_stream);
-        for (hipStream_t x : d.same_st)
-          if (x) (void)hipStreamSynchronize(x);
-      }
-      throw;
-    }
-    const avp::Counts done = avp::count(job_first, J, h_chk.data(), kc);
+    });
+    const avp::Counts done = avp::count(job_first, J, h_chk.data(), p.k);
     st.jobs_checked = done.jobs;
     st.miller_items = done.items;
     st.miller_chunks = done.chunks;

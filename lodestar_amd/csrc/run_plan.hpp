@@ -108,6 +108,15 @@ inline void dedupe_messages(const uint8_t* ms, uint32_t n, uint64_t key, std::ve
   }
 }
 
+// The same for a helper call (helpers.cpp): msg_idx as above; the value is the unique messages packed in that order.
+inline std::vector<uint8_t> unique_messages(const uint8_t* ms, uint32_t n, uint64_t key, std::vector<uint32_t>& msg_idx) {
+  std::vector<uint32_t> uniq;
+  dedupe_messages(ms, n, key, msg_idx, uniq);
+  std::vector<uint8_t> packed(uniq.size() * 32);
+  for (size_t u = 0; u < uniq.size(); u++) memcpy(packed.data() + u * 32, ms + (size_t)uniq[u] * 32, 32);
+  return packed;
+}
+
 // chunkifyMaximizeChunkSize (reference multithread/utils.ts:4-19): floor(len / min) chunks of ceil(len / count)
 // items, or one chunk when that count is <= 1.  Returns the items per chunk.
 inline uint32_t chunk_size(uint32_t len, uint32_t min_per_chunk) {
