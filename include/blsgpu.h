@@ -18,6 +18,11 @@
  *   blsgpu_destroy                  <- IBlsVerifier.close (chain/bls/interface.ts:45)
  *   blsgpu_aggregate_pubkeys        <- PublicKey.aggregate(pks).toBytes() (chain/bls/utils.ts:5-16,
  *                                      multithread/index.ts:160)
+ *   blsgpu_committees_upload        <- the epoch's shufflings the aggregate sets draw their committees from
+ *                                      (state-transition epochCache getBeaconCommittee / the sync committee's indices)
+ *   blsgpu_aggregate_pubkeys_bits   <- getAttestingIndices(committee, aggregationBits) / the sync aggregate's bit vector
+ *                                      (getSyncCommitteeSignatureSet) followed by getAggregatedPubkey(set).toBytes()
+ *                                      (chain/bls/utils.ts:5-16): the aggregated key straight from the bits
  *   blsgpu_aggregate_signatures     <- Signature.aggregate(sigs.map(fromBytes)).toBytes(), the op pools' fold of every
  *                                      verified signature into a running aggregate (beacon-node/src/chain/opPools/
  *                                      attestationPool.ts, aggregatedAttestationPool.ts, syncCommitteeMessagePool.ts,
@@ -78,7 +83,9 @@ extern "C" {
  * BLSGPU_SAME_BLOCK_CHECK of blsgpu_verify_same_message, which was refused before), blsgpu_aggregate_verify,
  * blsgpu_aggregate_verify_form (with blsgpu_aggregate_verify_stats and the BLSGPU_AV_* flags),
  * blsgpu_verify_same_message_agg, blsgpu_same_message_agg_lanes, blsgpu_pubkeys_upload_compressed (with
- * BLSGPU_PK_VALIDATE), blsgpu_pubkeys_read. */
+ * BLSGPU_PK_VALIDATE), blsgpu_pubkeys_read, blsgpu_committees_upload, blsgpu_committees_count,
+ * blsgpu_aggregate_pubkeys_bits (with blsgpu_committee_bits_stats and BLSGPU_BITS_NO_COMPLEMENT),
+ * blsgpu_committee_bits_mode, blsgpu_committee_bits_lanes. */
 #define BLSGPU_ABI_VERSION 8
 
 /* blsgpu_batch.job_flags bits (reference VerifySignatureOpts, chain/bls/interface.ts:3-18) */
@@ -309,6 +316,66 @@ int blsgpu_chunkify(uint32_t len, uint32_t min_per_chunk, uint32_t* chunk_first,
  * identity is encoded as the identity. */
 int blsgpu_aggregate_pubkeys(blsgpu_ctx* ctx, const blsgpu_batch* b, uint8_t* out, uint32_t out_len,
                              int8_t* status);
+
+/* The committee store (device 0, beside the pubkey table): the shufflings the aggregate sets are born from.  An aggregate
+ * ISignatureSet is a committee plus participation bits -- getAttestingIndices(committee, aggregationBits)
+ * (state-transition/src/cache/epochCache.ts; Electra: up to 64 committees per aggregate), the sync aggregate's 512-bit
+ * vector (getSyncCommitteeSignatureSet, state-transition/src/signatureSets/syncCommittee.ts) -- and the reference expands
+ * the bits into index lists on the main thread before getAggregatedPubkey (chain/bls/utils.ts:5-16) adds every key.
+ * With the committees stored, blsgpu_aggregate_pubkeys_bits takes the bits themselves.
+ *
+ * blsgpu_committees_upload truncates and appends: committees with id >= first_committee are dropped, then committees
+ * [first_committee, first_committee + n) are stored, committee first_committee + c being the table indices
+ * members[committee_first[c] .. committee_first[c + 1]) (committee_first is [n + 1], starts at 0 and strictly
+ * increases; members may repeat).  first_committee = 0 replaces the store, first_committee = blsgpu_committees_count
+ * appends the next epoch's shuffling, n == 0 only truncates.  The upload computes every new committee's sum of keys on
+ * the device and keeps it with the committee (a sum may be the identity).  BLSGPU_ERR_ARGS with nothing stored or
+ * dropped: a null ctx, null pointers with n > 0, first_committee beyond the count (no gaps), an empty committee, a
+ * member >= blsgpu_pubkeys_count, more than 1 << 20 members in the call.  A HIP failure returns BLSGPU_DEVICE_ERROR and
+ * leaves the store truncated at first_committee.
+ * A pubkey upload (either encoding) that overwrites existing table rows -- first_index below the table's size before it
+ * -- drops the whole store: blsgpu_committees_count becomes 0.  Appending rows keeps it. */
+int blsgpu_committees_upload(blsgpu_ctx* ctx, uint32_t first_committee, uint32_t n,
+                             const uint32_t* committee_first /* [n + 1] */, const uint32_t* members);
+uint32_t blsgpu_committees_count(const blsgpu_ctx* ctx);
+
+#define BLSGPU_BITS_NO_COMPLEMENT 1u /* diagnostics / tests: always sum the participants */
+
+typedef struct blsgpu_committee_bits_stats {
+  uint32_t segments, segments_complemented;
+  uint32_t keys_present;                /* set bits over the call */
+  uint32_t keys_added, keys_subtracted; /* table rows the kernel actually gathered */
+  uint32_t lanes;                       /* lanes per set */
+  double device_ms;
+} blsgpu_committee_bits_stats;
+
+/* getAggregatedPubkey(set).toBytes() (chain/bls/utils.ts:5-16) for n_sets aggregate sets given as committees plus
+ * participation bits.  Set s owns segments [set_seg_first[s], set_seg_first[s + 1]); segment k is the stored committee
+ * seg_committee[k] (the same committee may appear twice in a set).  The set's bit string is the concatenation, in
+ * segment order, of one bit per member of each segment's committee, in SSZ bit order (bit i = byte[i / 8] >> (i % 8) & 1;
+ * the caller strips a Bitlist's delimiter bit); it occupies exactly ceil(total bits / 8) bytes at
+ * bits + set_bits_first[s], its padding bits zero.  At most 1 << 20 sets, 1 << 22 segments and 1 << 31 bits per call.
+ * out[out_len * s] and status[s] are byte for byte what blsgpu_aggregate_pubkeys answers in table mode for the
+ * expanded index lists: EMPTY_AGGREGATE and zero bytes for a set with no bit set (or no segment), the identity
+ * encoding for a sum equal to the identity.  blsgpu_verify takes `out` (out_len 96) as pk_bytes in bytes mode.
+ * A segment is taken by complement -- the committee's stored sum minus the absent members' keys -- iff
+ * absent + 1 < present (blsgpu_committee_bits_mode: 0 direct, 1 complement); BLSGPU_BITS_NO_COMPLEMENT sums the
+ * participants of every segment.  The flag never changes an answer; stats (nullable) counts what was done.
+ * BLSGPU_ERR_ARGS before anything reaches the device, with nothing written: a null pointer other than stats, an out_len
+ * other than 48 / 96, an unknown flag, offsets not non-decreasing from 0, a committee id >= blsgpu_committees_count, a
+ * bit string of the wrong length, a non-zero padding bit.  n_sets == 0 returns BLSGPU_OK (after the pointer, out_len and flag
+ * checks).  A HIP failure returns BLSGPU_DEVICE_ERROR with nothing written.  Synchronous, on device 0 like the other
+ * helper calls. */
+int blsgpu_aggregate_pubkeys_bits(blsgpu_ctx* ctx, uint32_t n_sets, const uint32_t* set_seg_first /* [n_sets + 1] */,
+                                  const uint32_t* seg_committee /* [n_segs] */,
+                                  const uint32_t* set_bits_first /* [n_sets + 1], byte offsets */, const uint8_t* bits,
+                                  uint32_t flags, uint8_t* out, uint32_t out_len /* 48 | 96 */, int8_t* status,
+                                  blsgpu_committee_bits_stats* stats /* nullable */);
+/* The complement rule for a segment of `size` members of which `present` participate (pure host code) */
+uint32_t blsgpu_committee_bits_mode(uint32_t size, uint32_t present, uint32_t flags);
+/* Lanes per set of a call of n_sets sets whose kernel gathers n_items points in all -- keys added, keys subtracted and
+ * one stored sum per complemented segment (pure host code): 64, 32, 16 or 8. */
+uint32_t blsgpu_committee_bits_lanes(uint32_t n_sets, uint32_t n_items);
 
 #define BLSGPU_AGG_VALIDATE 1u /* Signature.fromBytes(.., validate = true): subgroup-check every signature */
 

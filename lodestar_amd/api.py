@@ -21,6 +21,9 @@ reference's own functions (same names in snake_case, same argument meaning and e
 * upload_pubkeys_compressed      state-transition/src/cache/pubkeyCache.ts:56-77 (syncPubkeys: PublicKey.fromBytes of
                                  every state.validators[i].pubkey; here the GPU decompresses into its table)
 * read_pubkeys                   index2pubkey[i].toBytes() of the keys the table holds
+* upload_committees              the epoch's shufflings (epochCache getBeaconCommittee, the sync committee's indices)
+* aggregate_pubkeys_from_bits    getAttestingIndices(committee, aggregationBits) / getSyncCommitteeSignatureSet's bit
+                                 walk followed by getAggregatedPubkey(set).toBytes() (chain/bls/utils.ts:5-16)
 * process_deposit_signature      state-transition/src/block/processDeposit.ts:54-64 (KeyValidate + verify;
                                  any error -> False: the deposit is skipped, not rejected)
 
@@ -93,6 +96,41 @@ def read_pubkeys(ctx: Context, first_index: int, n: int, compressed=False):
     k = 48 if compressed else 96
     out = ctx.read_pubkeys(first_index, n, k)
     return [out[k * i: k * i + k] for i in range(n)]
+
+
+def upload_committees(ctx: Context, first_committee: int, committees):
+    """Stores `committees` (a list of lists of table indices) as committees first_committee, first_committee + 1, ...
+    after dropping the stored committees from first_committee on: 0 replaces the store, ctx.committees_count appends
+    the next epoch's shuffling.  ValueError for what the library refuses (an empty committee, an index beyond the
+    table, a gap)."""
+    committees = [np.asarray(c, dtype=np.int64).reshape(-1) for c in committees]
+    if any(len(c) and (c.min() < 0 or c.max() > 0xFFFFFFFF) for c in committees):
+        raise ValueError("committee members must be table indices")
+    first = np.cumsum([0] + [len(c) for c in committees])
+    members = np.concatenate(committees) if committees else np.zeros(0, np.int64)
+    ctx.upload_committees(first_committee, first, members)
+
+
+def aggregate_pubkeys_from_bits(ctx: Context, sets, compressed=False, no_complement=False):
+    """getAggregatedPubkey(set).toBytes() for aggregate sets given the way they are born: `sets` is a list of sets, a
+    set a list of (committee id, participation bits) pairs -- one bit (any truthy value) per member of that stored
+    committee, as getAttestingIndices(committee, aggregationBits) reads them.  Returns a list of 96-byte uncompressed
+    (or 48-byte compressed) keys, None for a set without a participant (the reference's EMPTY_AGGREGATE_ARRAY)."""
+    from lodestar_amd.native import BITS_NO_COMPLEMENT, EMPTY_AGGREGATE
+
+    seg_first, bits_first, seg, packed = [0], [0], [], []
+    for s in sets:
+        flat = []
+        for committee, bits in s:
+            seg.append(int(committee))
+            flat.append(np.asarray(bits, dtype=bool).reshape(-1))
+        seg_first.append(len(seg))
+        packed.append(np.packbits(np.concatenate(flat) if flat else np.zeros(0, bool), bitorder="little"))
+        bits_first.append(bits_first[-1] + len(packed[-1]))
+    buf = np.concatenate(packed) if packed else np.zeros(0, np.uint8)
+    out, st, _ = ctx.aggregate_pubkeys_bits(seg_first, seg, bits_first, buf, BITS_NO_COMPLEMENT if no_complement else 0,
+                                            48 if compressed else 96)
+    return [None if st[i] == EMPTY_AGGREGATE else out[i] for i in range(len(out))]
 
 
 def fast_aggregate_verify(ctx: Context, pubkeys48, message: bytes, signature: bytes) -> bool:

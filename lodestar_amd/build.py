@@ -15,7 +15,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.environ.get("BLSGPU_LIB") or os.path.join(PKG, "libblsgpu.so")  # override: tuning variants
 ARCH = os.environ.get("BLSGPU_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-SOURCES = ["k_sig.hip", "k_msm.hip", "k_hash.hip", "k_hmap.hip", "k_pk.hip", "k_sigagg.hip", "k_awr.hip", "k_same.hip", "k_aggverify.hip", "k_miller.hip", "k_group.hip", "k_inv.hip", "k_ssz.hip", "k_debug.hip", "k_tower_debug.hip", "k_curve_debug.hip", "k_coop_debug.hip",
+SOURCES = ["k_sig.hip", "k_msm.hip", "k_hash.hip", "k_hmap.hip", "k_pk.hip", "k_committee.hip", "k_sigagg.hip", "k_awr.hip", "k_same.hip", "k_aggverify.hip", "k_miller.hip", "k_group.hip", "k_inv.hip", "k_ssz.hip", "k_debug.hip", "k_tower_debug.hip", "k_curve_debug.hip", "k_coop_debug.hip",
            "runtime.cpp", "pipeline.cpp", "helpers.cpp"]
 
 
@@ -50,7 +50,7 @@ def tu_defines():
 # C2 equal within noise (3.40M vs 3.39M at 20 steps, 3.83M vs 3.84M at 100; profiles/r06_hash_sched_ab.json).
 _ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 _MINREG = ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"]
-TU_CFLAGS = {"k_hash.hip": _MINREG, "k_pk.hip": _ILP}
+TU_CFLAGS = {"k_hash.hip": _MINREG, "k_pk.hip": _ILP, "k_committee.hip": _ILP}
 
 
 def tu_cflags():
@@ -79,7 +79,7 @@ def _tu_deps(src):
     if src.endswith(".cpp"):
         return [os.path.join(CSRC, f) for f in (src, "kernels.h", "batch_rand.hpp", "runtime_internal.hpp",
                                                 "run_plan.hpp", "options.hpp", "call_plan.hpp", "helper_layout.hpp",
-                                                "miller_plan.hpp", "aggverify_plan.hpp", "same_plan.hpp",
+                                                "miller_plan.hpp", "aggverify_plan.hpp", "same_plan.hpp", "committee_plan.hpp",
                                                 "helper_buffers.hpp")] + [
             os.path.join(ROOT, "include", "blsgpu.h")]
     return [os.path.join(CSRC, src)] + _headers()

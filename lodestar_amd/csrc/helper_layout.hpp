@@ -34,6 +34,19 @@ struct AggPubkeys {
   }
 };
 
+// blsgpu_aggregate_pubkeys_bits: n sets over n_segs segments, bits_bytes bytes of bit strings.  d_in: set_seg_first |
+// segment descriptors | set_bits_first | bits | present_first (a set's running count of set bits: what k_pk_serialize
+// reads as set_pk_first) | out | status.  d_work: a Jacobian sum per set.
+struct AggPubkeysBits {
+  size_t ssf, seg, sbf, bits, present, out, st, total, work_words;
+  AggPubkeysBits(size_t n, size_t n_segs, size_t bits_bytes, size_t out_len) {
+    Carve c;
+    ssf = c.take((n + 1) * 4), seg = c.take(n_segs * 4), sbf = c.take((n + 1) * 4), bits = c.take(bits_bytes);
+    present = c.take((n + 1) * 4), out = c.take(n * out_len), st = c.take(3 * n);
+    total = c.end, work_words = n * kG1J;
+  }
+};
+
 // blsgpu_aggregate_signatures.  d_in: group_first | sig_len | sigs | out | first_bad | group status | signature
 // status | signature flags.  d_work: sig_aff | a Jacobian sum per group (w_agg).
 struct AggSigs {

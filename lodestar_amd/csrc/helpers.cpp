@@ -3,6 +3,7 @@
 // table_stream, in Device::helper's buffers; helper_call is the envelope they share and helper_layout.hpp says where
 // every field of their device arenas lies.  The asynchronous verification pipeline is runtime.cpp and pipeline.cpp.
 #include "aggverify_plan.hpp"
+#include "committee_plan.hpp"
 #include "helper_buffers.hpp"
 #include "helper_layout.hpp"
 #include "runtime_internal.hpp"
@@ -12,7 +13,11 @@ using namespace blsgpu_rt;
 namespace hl = helper_layout;
 namespace avp = aggverify_plan;
 namespace sp = same_plan;
+namespace cmp = committee_plan;
 
+static_assert(cmp::kNoComplement == BLSGPU_BITS_NO_COMPLEMENT && cmp::kErrArgs == BLSGPU_ERR_ARGS &&
+                  cmp::kMaxUploadMembers == 1u << 20,
+              "committee_plan.hpp restates include/blsgpu.h");
 static_assert(hl::kFp == W_FP && hl::kG1A == W_G1A && hl::kG1J == W_G1J && hl::kG2A == W_G2A && hl::kG2J == W_G2J &&
                   hl::kFp12 == W_FP12 && hl::kAwrTabWords == AWR_TAB_WORDS && hl::kMillerLineWords == kMillerLineWords,
               "helper_layout.hpp restates the element widths of kernels.h");
@@ -42,6 +47,22 @@ int helper_call(blsgpu_ctx* ctx, bool reads_table, Body body) {
   } catch (HipError&) {
     return BLSGPU_DEVICE_ERROR;
   }
+}
+
+// Grows a buffer of the committee store to `need` words, keeping its first `keep` (DevBuf::ensure keeps nothing): the
+// way the pubkey table grows.  Ends synchronized when it grew.
+void grow_keeping(DevBuf<uint32_t>& b, size_t keep, size_t need, hipStream_t s) {
+  if (need <= b.cap) return;
+  DevBuf<uint32_t> nb;
+  nb.ensure(std::max(need, b.cap + b.cap / 2));
+  if (keep) HIPCHK(hipMemcpyAsync(nb.p, b.p, keep * 4, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  b.release();
+  b = nb;
+}
+// the device's committee store and pubkey table as the kernels take them (under table_mu)
+CommitteeStore committee_store(Device& d) {
+  return CommitteeStore{d.cm_first.p, d.cm_members.p, d.cm_sums.p, d.table.p, d.table_n};
 }
 
 // The grouped calls' inputs: signatures [group_first[g], group_first[g + 1]) form group g; the same-message calls
@@ -875,6 +896,123 @@ int blsgpu_pubkeys_read(blsgpu_ctx* ctx, uint32_t first_index, uint32_t n, uint8
     HIPCHK(hipStreamSynchronize(s));
     return BLSGPU_OK;
   });
+}
+
+// ---- the committee store and the aggregation from participation bits (the host decisions are
+// committee_plan.hpp, the kernels k_committee.hip)
+uint32_t blsgpu_committees_count(const blsgpu_ctx* ctx) {
+  if (!ctx || ctx->devs.empty()) return 0;
+  Device& d = *ctx->devs[0];
+  std::shared_lock<std::shared_mutex> lk(d.table_mu);
+  return d.cm_n;
+}
+
+int blsgpu_committees_upload(blsgpu_ctx* ctx, uint32_t first_committee, uint32_t n, const uint32_t* committee_first,
+                             const uint32_t* members) {
+  if (!ctx || ctx->devs.empty()) return BLSGPU_ERR_ARGS;
+  if (!enter(ctx)) return BLSGPU_ERR_CLOSED;
+  struct Leave {
+    blsgpu_ctx* ctx;
+    ~Leave() { leave(ctx); }
+  } leave_on_exit{ctx};
+  Device& d = *ctx->devs[0];
+  try {
+    // the helper lock for table_stream, the table lock exclusively: no bits call reads the store meanwhile
+    std::lock_guard<std::mutex> helper(d.helper_mu);
+    std::unique_lock<std::shared_mutex> tl(d.table_mu);
+    if (cmp::check_upload(first_committee, n, committee_first, members, d.cm_n, d.table_n)) return BLSGPU_ERR_ARGS;
+    HIPCHK(hipSetDevice(d.id));
+    hipStream_t s = d.table_stream;
+    // truncate; a HIP failure below leaves the store so
+    d.cm_n = first_committee;
+    d.cm_first_host.resize((size_t)first_committee + 1, 0);
+    if (n == 0) return BLSGPU_OK;
+    const uint32_t base = d.cm_first_host[first_committee], total = committee_first[n], count = first_committee + n;
+    // (entry first_committee of cm_first is rewritten below with the rest: the kept part ends before it)
+    grow_keeping(d.cm_first, first_committee, (size_t)count + 1, s);
+    grow_keeping(d.cm_members, base, (size_t)base + total, s);
+    grow_keeping(d.cm_sums, (size_t)first_committee * W_CSUM, (size_t)count * W_CSUM, s);
+    std::vector<uint32_t> first((size_t)n + 1);  // copied from: lives until the synchronize
+    for (uint32_t c = 0; c <= n; c++) first[c] = base + committee_first[c];
+    HIPCHK(hipMemcpyAsync(d.cm_first.p + first_committee, first.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d.cm_members.p + base, members, (size_t)total * 4, hipMemcpyHostToDevice, s));
+    launch_committee_sums(committee_store(d), first_committee, n, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    d.cm_first_host.insert(d.cm_first_host.end(), first.begin() + 1, first.end());
+    d.cm_n = count;
+    return BLSGPU_OK;
+  } catch (HipError&) {
+    return BLSGPU_DEVICE_ERROR;
+  }
+}
+
+uint32_t blsgpu_committee_bits_mode(uint32_t size, uint32_t present, uint32_t flags) {
+  return cmp::mode(size, present, flags);
+}
+uint32_t blsgpu_committee_bits_lanes(uint32_t n_sets, uint32_t n_items) { return cmp::lanes(n_sets, n_items); }
+
+int blsgpu_aggregate_pubkeys_bits(blsgpu_ctx* ctx, uint32_t n_sets, const uint32_t* set_seg_first,
+                                  const uint32_t* seg_committee, const uint32_t* set_bits_first, const uint8_t* bits,
+                                  uint32_t flags, uint8_t* out, uint32_t out_len, int8_t* status,
+                                  blsgpu_committee_bits_stats* stats) {
+  if (!ctx || ctx->devs.empty()) return BLSGPU_ERR_ARGS;
+  if (cmp::check_call(n_sets, set_seg_first, seg_committee, set_bits_first, bits, flags, out, out_len, status))
+    return BLSGPU_ERR_ARGS;
+  if (n_sets == 0) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    return BLSGPU_OK;
+  }
+  const uint32_t n = n_sets;
+  std::vector<uint8_t> h_out((size_t)n * out_len);  // results reach the caller only when every one was computed
+  std::vector<int8_t> h_st(n);
+  blsgpu_committee_bits_stats st{};
+  const int rc = helper_call(ctx, true, [&](Device& d, Slot& sl, hipStream_t s) -> int {
+    cmp::Plan p;  // (copied from: lives until the synchronize)
+    if (cmp::make_plan(n, set_seg_first, seg_committee, set_bits_first, bits, flags, d.cm_first_host.data(), d.cm_n, p))
+      return BLSGPU_ERR_ARGS;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hl::AggPubkeysBits l(n, p.n_segs, p.bits_bytes, out_len);
+    sl.d_in.ensure(l.total);
+    sl.d_work.ensure(l.work_words);
+    uint8_t* din = sl.d_in.p;
+    HIPCHK(hipMemcpyAsync(din + l.ssf, set_seg_first, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(din + l.sbf, set_bits_first, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(din + l.present, p.present_first.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, s));
+    if (p.n_segs) HIPCHK(hipMemcpyAsync(din + l.seg, p.seg_desc.data(), (size_t)p.n_segs * 4, hipMemcpyHostToDevice, s));
+    if (p.bits_bytes) HIPCHK(hipMemcpyAsync(din + l.bits, bits, p.bits_bytes, hipMemcpyHostToDevice, s));
+    CommitteeBits a{};
+    a.n_sets = n;
+    a.set_seg_first = reinterpret_cast<uint32_t*>(din + l.ssf);
+    a.seg_desc = reinterpret_cast<uint32_t*>(din + l.seg);
+    a.set_bits_first = reinterpret_cast<uint32_t*>(din + l.sbf);
+    a.bits = din + l.bits;
+    a.pk_jac = sl.d_work.p;
+    a.status = reinterpret_cast<int8_t*>(din + l.st);
+    launch_pk_bits(committee_store(d), a, p.counts.lanes, s);
+    // k_pk_serialize as blsgpu_aggregate_pubkeys runs it: a set's keys are its set bits (EMPTY_AGGREGATE for none)
+    PipelineBuffers pb{};
+    pb.n = n;
+    pb.set_pk_first = reinterpret_cast<uint32_t*>(din + l.present);
+    pb.pk_jac = a.pk_jac;
+    pb.status = a.status;
+    launch_pk_serialize(pb, n, din + l.out, out_len, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_out.data(), din + l.out, h_out.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_st.data(), din + l.st, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const cmp::Counts& c = p.counts;
+    st.segments = c.segments, st.segments_complemented = c.segments_complemented, st.keys_present = c.keys_present;
+    st.keys_added = c.keys_added, st.keys_subtracted = c.keys_subtracted, st.lanes = c.lanes;
+    st.device_ms = ms_since(t0);
+    return BLSGPU_OK;
+  });
+  if (rc == BLSGPU_OK) {
+    memcpy(out, h_out.data(), h_out.size());
+    memcpy(status, h_st.data(), n);
+    if (stats) *stats = st;
+  }
+  return rc;
 }
 
 int blsgpu_signing_roots(blsgpu_ctx* ctx, int kind, uint32_t n, const uint8_t* objects, uint32_t object_stride,

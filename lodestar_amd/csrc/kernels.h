@@ -206,6 +206,32 @@ void launch_pk_table_read(const uint32_t* table, uint32_t first, uint32_t n, uin
                           hipStream_t s);
 // serialize the per-set aggregate (pk_jac) to 96-byte uncompressed or 48-byte compressed encodings
 void launch_pk_serialize(const PipelineBuffers& b, uint32_t n_sets, uint8_t* out, uint32_t out_len, hipStream_t s);
+// The committee store (k_committee.hip): committee c is members[first[c] .. first[c + 1]) (table
+// indices) and keeps the sum of its members' keys in sums[W_CSUM c ..], a row shaped like a table row: affine x | y and
+// four pad words, the first of them 1 (x, y zero) when the sum is the identity.
+#define W_CSUM 32
+struct CommitteeStore {
+  const uint32_t* first;
+  const uint32_t* members;
+  uint32_t* sums;
+  const uint32_t* pk_table;
+  uint32_t pk_table_n;
+};
+// sums of committees [c0, c0 + n): the segmented G1 sum on the lanes per committee launch_pk_aggregate would take
+void launch_committee_sums(const CommitteeStore& st, uint32_t c0, uint32_t n, hipStream_t s);
+// blsgpu_aggregate_pubkeys_bits: every set's aggregated key from its participation bits, on L lanes per set (64, 32,
+// 16 or 8: committee_plan.hpp lanes), into pk_jac (W_G1J SoA, stride n_sets), with status[2 n_sets + set] = 0.  Set s
+// owns segments seg_desc[set_seg_first[s] .. set_seg_first[s + 1]) and the bit string at bits + set_bits_first[s].
+struct CommitteeBits {
+  uint32_t n_sets;
+  const uint32_t* set_seg_first;
+  const uint32_t* seg_desc;
+  const uint32_t* set_bits_first;
+  const uint8_t* bits;
+  uint32_t* pk_jac;
+  int8_t* status;
+};
+void launch_pk_bits(const CommitteeStore& st, const CommitteeBits& a, uint32_t L, hipStream_t s);
 // KeyValidate of untrusted 48/96-byte pubkeys (decode + G1 subgroup check) -> 96-byte uncompressed
 void launch_key_validate(const uint8_t* pks, uint32_t n, uint32_t pk_len, uint32_t stride, uint8_t* out96,
                          int8_t* status, hipStream_t s);

@@ -557,6 +557,9 @@ void destroy_device(Device* d) {
     if (e) (void)hipEventDestroy(e);
   d->helper.release_all();
   d->table.release();
+  d->cm_first.release();
+  d->cm_members.release();
+  d->cm_sums.release();
   if (d->table_stream) (void)hipStreamDestroy(d->table_stream);
   delete d;
 }
@@ -855,6 +858,8 @@ int table_upload(blsgpu_ctx* ctx, uint32_t first_index, const uint8_t* keys, uin
         HIPCHK(hipMemcpyAsync(d->table.p + (size_t)first_index * W_PKTAB, tmp, (size_t)n * W_PKTAB * 4,
                               hipMemcpyDeviceToDevice, ts));
         HIPCHK(hipStreamSynchronize(ts));
+        // rows were overwritten: the stored committee sums (helpers.cpp) may no longer be their members' sums
+        if (first_index < d->table_n) d->cm_n = 0, d->cm_first_host.clear();
         d->table_n = std::max(d->table_n, need);
       }
       return err;

@@ -259,6 +259,12 @@ struct Device {
   std::shared_mutex table_mu;
   DevBuf<uint32_t> table;
   uint32_t table_n = 0;
+  // committee store (used on device 0; blsgpu_committees_upload, helpers.cpp), under table_mu like the table: committee
+  // c is cm_members[cm_first[c] .. cm_first[c + 1]) and cm_sums holds its members' sum (kernels.h CommitteeStore).
+  // cm_first_host mirrors cm_first ([cm_n + 1], or empty).  A table upload that overwrites rows empties it.
+  DevBuf<uint32_t> cm_first, cm_members, cm_sums;
+  std::vector<uint32_t> cm_first_host;
+  uint32_t cm_n = 0;
   // slots, each served by one dispatcher thread taking tasks from this device's queue
   std::mutex q_mu;
   std::condition_variable q_cv;

@@ -66,8 +66,14 @@ EXPORTED_SYMBOLS = [
     "blsgpu_same_message_agg_lanes",
     "blsgpu_pubkeys_upload_compressed",
     "blsgpu_pubkeys_read",
+    "blsgpu_committees_upload",
+    "blsgpu_committees_count",
+    "blsgpu_aggregate_pubkeys_bits",
+    "blsgpu_committee_bits_mode",
+    "blsgpu_committee_bits_lanes",
 ]
 PK_VALIDATE = 1  # BLSGPU_PK_VALIDATE: the uploaded keys are untrusted, KeyValidate each
+BITS_NO_COMPLEMENT = 1  # BLSGPU_BITS_NO_COMPLEMENT: diagnostics / tests, always sum the participants
 SAME_LANE_FORMS = 1
 SAME_BLOCK_CHECK = 4  # BLSGPU_SAME_BLOCK_CHECK: one check per block of 1024 groups, then the descent
 # blsgpu_aggregate_verify flags
@@ -133,6 +139,18 @@ class AggregateVerifyStats(ctypes.Structure):
         ("miller_chunks", ctypes.c_uint32),
         ("form", ctypes.c_uint32),
         ("jobs_checked", ctypes.c_uint32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
+class CommitteeBitsStats(ctypes.Structure):
+    _fields_ = [
+        ("segments", ctypes.c_uint32),
+        ("segments_complemented", ctypes.c_uint32),
+        ("keys_present", ctypes.c_uint32),
+        ("keys_added", ctypes.c_uint32),
+        ("keys_subtracted", ctypes.c_uint32),
+        ("lanes", ctypes.c_uint32),
         ("device_ms", ctypes.c_double),
     ]
 
@@ -230,6 +248,16 @@ def load():
     lib.blsgpu_pubkeys_upload_compressed.restype = ctypes.c_int
     lib.blsgpu_pubkeys_read.argtypes = [vp, u32, u32, vp, u32]
     lib.blsgpu_pubkeys_read.restype = ctypes.c_int
+    lib.blsgpu_committees_upload.argtypes = [vp, u32, u32, vp, vp]
+    lib.blsgpu_committees_upload.restype = ctypes.c_int
+    lib.blsgpu_committees_count.argtypes = [vp]
+    lib.blsgpu_committees_count.restype = u32
+    lib.blsgpu_aggregate_pubkeys_bits.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, u32, vp, vp]
+    lib.blsgpu_aggregate_pubkeys_bits.restype = ctypes.c_int
+    lib.blsgpu_committee_bits_mode.argtypes = [u32, u32, u32]
+    lib.blsgpu_committee_bits_mode.restype = u32
+    lib.blsgpu_committee_bits_lanes.argtypes = [u32, u32]
+    lib.blsgpu_committee_bits_lanes.restype = u32
     _lib = lib
     return lib
 
@@ -328,6 +356,18 @@ def aggregate_verify_form(n_items, flags=0):
     jobs plus one item per such job (C-ABI blsgpu_aggregate_verify_form, pure host code): 0 = cooperative, 1 = lane
     forms."""
     return int(load().blsgpu_aggregate_verify_form(n_items, flags))
+
+
+def committee_bits_mode(size, present, flags=0):
+    """How blsgpu_aggregate_pubkeys_bits takes a segment of `size` members of which `present` participate (C-ABI
+    blsgpu_committee_bits_mode, pure host code): 0 = sums the participants, 1 = by complement."""
+    return int(load().blsgpu_committee_bits_mode(size, present, flags))
+
+
+def committee_bits_lanes(n_sets, n_items):
+    """Lanes per set blsgpu_aggregate_pubkeys_bits gives a call of n_sets sets that gathers n_items points (C-ABI
+    blsgpu_committee_bits_lanes, pure host code): 64, 32, 16 or 8."""
+    return int(load().blsgpu_committee_bits_lanes(n_sets, n_items))
 
 
 def randomness_words(n, seed):
@@ -546,6 +586,57 @@ class Context:
     @property
     def pubkeys_count(self):
         return self._lib.blsgpu_pubkeys_count(self.h)
+
+    def upload_committees(self, first_committee: int, committee_first, members):
+        """blsgpu_committees_upload: drops the stored committees with id >= first_committee, then stores committees
+        [first_committee, first_committee + n), committee c of the call being the table indices
+        members[committee_first[c]: committee_first[c + 1]].  ValueError for a refused call (BLSGPU_ERR_ARGS)."""
+        cf = np.ascontiguousarray(committee_first, dtype=np.uint32)
+        mem = np.ascontiguousarray(members, dtype=np.uint32)
+        if cf.ndim != 1 or len(cf) == 0:
+            raise ValueError("committee_first needs n + 1 >= 1 entries")
+        n = len(cf) - 1
+        if len(mem) != int(cf[-1]):
+            raise ValueError(f"committee_first ends at {int(cf[-1])}, got {len(mem)} members")
+        rc = self._lib.blsgpu_committees_upload(self.h, first_committee, n, cf.ctypes.data if n else None,
+                                                mem.ctypes.data if n else None)
+        if rc == ERR_ARGS:
+            raise ValueError("blsgpu_committees_upload -> BLSGPU_ERR_ARGS")
+        if rc != OK:
+            raise RuntimeError(f"blsgpu_committees_upload -> {code_name(rc)}")
+
+    @property
+    def committees_count(self):
+        return self._lib.blsgpu_committees_count(self.h)
+
+    def aggregate_pubkeys_bits(self, set_seg_first, seg_committee, set_bits_first, bits, flags=0, out_len=96):
+        """blsgpu_aggregate_pubkeys_bits: the aggregated key of every set from its committees' participation bits.
+        Returns (list of out_len-byte encodings, status int8 array, CommitteeBitsStats).  ValueError for a refused
+        call (BLSGPU_ERR_ARGS), RuntimeError for a call-level failure."""
+        ssf = np.ascontiguousarray(set_seg_first, dtype=np.uint32)
+        sbf = np.ascontiguousarray(set_bits_first, dtype=np.uint32)
+        seg = np.ascontiguousarray(seg_committee, dtype=np.uint32)
+        if ssf.ndim != 1 or len(ssf) == 0 or sbf.shape != ssf.shape:
+            raise ValueError("set_seg_first and set_bits_first need n_sets + 1 >= 1 entries each")
+        n = len(ssf) - 1
+        buf = _u8(bits)
+        if len(seg) < int(ssf[-1]) or len(buf) < int(sbf[-1]):
+            raise ValueError("seg_committee / bits shorter than the offsets say")
+        if len(seg) == 0:
+            seg = np.zeros(1, np.uint32)
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        out = np.zeros(max(n, 1) * out_len, np.uint8)
+        st = np.zeros(max(n, 1), np.int8)
+        stats = CommitteeBitsStats()
+        rc = self._lib.blsgpu_aggregate_pubkeys_bits(self.h, n, ssf.ctypes.data, seg.ctypes.data, sbf.ctypes.data,
+                                                     buf.ctypes.data, flags, out.ctypes.data, out_len, st.ctypes.data,
+                                                     ctypes.byref(stats))
+        if rc == ERR_ARGS:
+            raise ValueError("blsgpu_aggregate_pubkeys_bits -> BLSGPU_ERR_ARGS")
+        if rc != OK:
+            raise RuntimeError(f"blsgpu_aggregate_pubkeys_bits -> {code_name(rc)}")
+        return [out[out_len * i: out_len * (i + 1)].tobytes() for i in range(n)], st[:n], stats
 
     def verify_raw(self, job_first_set, sigs, sig_len, msgs, pk_bytes=None, set_pk_first=None, pk_index=None,
                    job_flags=None, sig_stride=None, seed=0x4C4F444553544152):

@@ -88,6 +88,35 @@ function jobError(code) {
   return new Error(`BLST_ERROR: ${name}`);
 }
 
+/**
+ * The arrays of addon.aggregatePubkeysFromBits: a set's bit string is the concatenation, bit for bit, of its segments'
+ * first bitLen bits, in exactly ceil(total / 8) bytes with zero padding.
+ */
+function packBitSets(sets) {
+  const setSegFirst = new Uint32Array(sets.length + 1);
+  const setBitsFirst = new Uint32Array(sets.length + 1);
+  let nSegs = 0;
+  sets.forEach((s, i) => {
+    let total = 0;
+    for (const seg of s) total += seg.bitLen;
+    nSegs += s.length;
+    setSegFirst[i + 1] = nSegs;
+    setBitsFirst[i + 1] = setBitsFirst[i] + Math.ceil(total / 8);
+  });
+  const segCommittee = new Uint32Array(nSegs);
+  const bits = new Uint8Array(setBitsFirst[sets.length]);
+  let k = 0;
+  sets.forEach((s, i) => {
+    let pos = 8 * setBitsFirst[i];
+    for (const seg of s) {
+      segCommittee[k++] = seg.committee;
+      for (let b = 0; b < seg.bitLen; b++, pos++)
+        if ((seg.bits[b >> 3] >> (b & 7)) & 1) bits[pos >> 3] |= 1 << (pos & 7);
+    }
+  });
+  return {setSegFirst, segCommittee, setBitsFirst, bits};
+}
+
 class BlsGpuVerifier {
   /**
    * @param {{devices?: number[], groupSets?: number, groupPolicy?: number, seed?: number,
@@ -158,6 +187,55 @@ class BlsGpuVerifier {
    */
   readPubkeys(firstIndex, n, opts = {}) {
     return addon.readPubkeys(this.ctx, firstIndex, n, opts.compressed ? 48 : 96);
+  }
+
+  /**
+   * The epoch's shufflings on the device (epochCache getBeaconCommittee, the sync committee's indices): drops the stored
+   * committees with id >= firstCommittee, then stores `committees` (arrays of validator indices into the device table)
+   * as ids firstCommittee, firstCommittee + 1, ...  0 replaces the store, committeesCount appends the next epoch's.
+   * Synchronous, like uploadPubkeys.  An upload that overwrites table rows empties the store.
+   * @param {number} firstCommittee
+   * @param {Array<ArrayLike<number>>} committees
+   */
+  uploadCommittees(firstCommittee, committees) {
+    const committeeFirst = new Uint32Array(committees.length + 1);
+    committees.forEach((c, i) => (committeeFirst[i + 1] = committeeFirst[i] + c.length));
+    const members = new Uint32Array(committeeFirst[committees.length]);
+    committees.forEach((c, i) => members.set(c, committeeFirst[i]));
+    addon.uploadCommittees(this.ctx, firstCommittee, committeeFirst, members);
+  }
+
+  get committeesCount() {
+    return addon.committeesCount(this.ctx);
+  }
+
+  /**
+   * getAggregatedPubkey(set).toBytes() (chain/bls/utils.ts:5-16) for aggregate sets given the way they are born, as
+   * committees plus participation bits, without expanding the bits on the main thread (getAttestingIndices,
+   * getSyncCommitteeSignatureSet): one device call, off the main thread.  A set is an array of {committee: stored id,
+   * bits: Uint8Array in SSZ bit order, bitLen: the committee's size} -- the uint8Array and bitLen of an ssz BitArray
+   * (a Bitlist without its delimiter bit); bits from bitLen on are ignored.  Resolves to one entry per set: the key's bytes (96 uncompressed -- what verifySignatureSets takes as a
+   * pubkey --, or 48 with {compressed: true}), or the Error "EMPTY_AGGREGATE_ARRAY" for a set without a participant.
+   * Rejects for malformed input (BLSGPU_ERR_ARGS), a call-level failure or a closed verifier.
+   * @param {Array<Array<{committee: number, bits: Uint8Array}>>} sets
+   * @param {{compressed?: boolean, noComplement?: boolean}} opts
+   * @returns {Promise<Array<Uint8Array | Error>>}
+   */
+  async aggregatePubkeysFromBits(sets, {compressed = false, noComplement = false} = {}) {
+    if (this.closed) throw new QueueError({code: QUEUE_ABORTED});
+    const {setSegFirst, segCommittee, setBitsFirst, bits} = packBitSets(sets);
+    const outLen = compressed ? 48 : 96;
+    const p = addon
+      .aggregatePubkeysFromBits(this.ctx, setSegFirst, segCommittee, setBitsFirst, bits, noComplement, outLen)
+      .then(
+        (r) => sets.map((_, i) => (r.status[i] === 0 ? r.out.slice(outLen * i, outLen * (i + 1)) : jobError(r.status[i]))),
+        (err) => {
+          throw err.code === QUEUE_ABORTED ? new QueueError({code: QUEUE_ABORTED}) : err;
+        }
+      );
+    this.inflight.add(p);
+    p.finally(() => this.inflight.delete(p)).catch(() => {});
+    return p;
   }
 
   registerPubkey(obj, index) {

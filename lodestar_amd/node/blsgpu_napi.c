@@ -1187,6 +1187,182 @@ static napi_value AggregateVerify(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+/* uploadCommittees(ctx, firstCommittee, committeeFirst Uint32Array [n + 1], members Uint32Array)  (synchronous, like
+ * uploadPubkeys): blsgpu_committees_upload */
+static napi_value UploadCommittees(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 4) {
+    napi_throw_type_error(env, NULL, "uploadCommittees(ctx, firstCommittee, committeeFirst, members)");
+    return NULL;
+  }
+  CtxBox* box = get_open_box(env, argv[0]);
+  if (!box) return NULL;
+  uint32_t first = 0;
+  CHECK(env, napi_get_value_uint32(env, argv[1], &first));
+  napi_typedarray_type t_cf, t_mem;
+  size_t n_cf = 0, n_mem = 0;
+  void *cf = NULL, *mem = NULL;
+  if (napi_get_typedarray_info(env, argv[2], &t_cf, &n_cf, &cf, NULL, NULL) != napi_ok || t_cf != napi_uint32_array ||
+      napi_get_typedarray_info(env, argv[3], &t_mem, &n_mem, &mem, NULL, NULL) != napi_ok ||
+      t_mem != napi_uint32_array) {
+    napi_throw_type_error(env, NULL, "uploadCommittees: committeeFirst and members Uint32Array expected");
+    return NULL;
+  }
+  /* the arrays must be as long as the offsets say before the library reads them */
+  if (n_cf < 1 || n_cf - 1 > 0xffffffffu || ((const uint32_t*)cf)[n_cf - 1] != n_mem)
+    return throw_code(env, "uploadCommittees", BLSGPU_ERR_ARGS);
+  const uint32_t n = (uint32_t)(n_cf - 1);
+  int rc = blsgpu_committees_upload(box->ctx, first, n, n ? (const uint32_t*)cf : NULL, n ? (const uint32_t*)mem : NULL);
+  if (rc != BLSGPU_OK) return throw_code(env, "uploadCommittees", rc);
+  return NULL;
+}
+
+static napi_value CommitteesCount(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  CtxBox* box = get_open_box(env, argv[0]);
+  if (!box) return NULL;
+  napi_value out;
+  CHECK(env, napi_create_uint32(env, blsgpu_committees_count(box->ctx), &out));
+  return out;
+}
+
+/* aggregatePubkeysFromBits: one blsgpu_aggregate_pubkeys_bits call as async work, with the lifetime rules of
+ * aggregateSignatures (inputs copied before it returns; close() refuses while a call is outstanding) */
+typedef struct {
+  CtxBox* box;
+  uint32_t n_sets, flags, out_len;
+  uint32_t* set_seg_first;
+  uint32_t* seg_committee;
+  uint32_t* set_bits_first;
+  uint8_t* bits;
+  uint8_t* out;
+  int8_t* status;
+  blsgpu_committee_bits_stats stats;
+  int rc;
+  napi_deferred deferred;
+  napi_async_work work;
+} BitsCall;
+
+static void bits_free(BitsCall* a) {
+  free(a->set_seg_first);
+  free(a->seg_committee);
+  free(a->set_bits_first);
+  free(a->bits);
+  free(a->out);
+  free(a->status);
+  free(a);
+}
+
+/* libuv worker thread */
+static void bits_execute(napi_env env, void* data) {
+  (void)env;
+  BitsCall* a = (BitsCall*)data;
+  a->rc = blsgpu_aggregate_pubkeys_bits(a->box->ctx, a->n_sets, a->set_seg_first, a->seg_committee, a->set_bits_first,
+                                        a->bits, a->flags, a->out, a->out_len, a->status, &a->stats);
+}
+
+/* JS main thread */
+static void bits_complete(napi_env env, napi_status st, void* data) {
+  BitsCall* a = (BitsCall*)data;
+  a->box->agg_pending--;
+  if (st != napi_ok || a->rc != BLSGPU_OK) {
+    const char* name = blsgpu_code_name(st != napi_ok ? BLSGPU_ERR_CLOSED : a->rc);
+    napi_value msg, code, err;
+    napi_create_string_utf8(env, name ? name : "BLSGPU_DEVICE_ERROR", NAPI_AUTO_LENGTH, &msg);
+    napi_create_string_utf8(env, name ? name : "BLSGPU_DEVICE_ERROR", NAPI_AUTO_LENGTH, &code);
+    napi_create_error(env, code, msg, &err);
+    napi_reject_deferred(env, a->deferred, err);
+  } else {
+    napi_value out, stats;
+    napi_create_object(env, &out);
+    napi_create_object(env, &stats);
+    set_u32(env, stats, "segments", a->stats.segments);
+    set_u32(env, stats, "segmentsComplemented", a->stats.segments_complemented);
+    set_u32(env, stats, "keysPresent", a->stats.keys_present);
+    set_u32(env, stats, "keysAdded", a->stats.keys_added);
+    set_u32(env, stats, "keysSubtracted", a->stats.keys_subtracted);
+    set_u32(env, stats, "lanes", a->stats.lanes);
+    set_num(env, stats, "deviceMs", a->stats.device_ms);
+    napi_set_named_property(env, out, "out", copy_out(env, napi_uint8_array, a->out, (size_t)a->n_sets * a->out_len, 1));
+    napi_set_named_property(env, out, "status", copy_out(env, napi_int8_array, a->status, a->n_sets, 1));
+    napi_set_named_property(env, out, "stats", stats);
+    napi_resolve_deferred(env, a->deferred, out);
+  }
+  napi_delete_async_work(env, a->work);
+  bits_free(a);
+}
+
+static napi_value AggregatePubkeysFromBits(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 7) {
+    napi_throw_type_error(
+        env, NULL, "aggregatePubkeysFromBits(ctx, setSegFirst, segCommittee, setBitsFirst, bits, noComplement, outLen)");
+    return NULL;
+  }
+  CtxBox* box = get_open_box(env, argv[0]);
+  if (!box) return NULL;
+  napi_typedarray_type t[4];
+  size_t len[4] = {0, 0, 0, 0};
+  void* p[4] = {NULL, NULL, NULL, NULL};
+  const napi_typedarray_type want[4] = {napi_uint32_array, napi_uint32_array, napi_uint32_array, napi_uint8_array};
+  for (int k = 0; k < 4; k++)
+    if (napi_get_typedarray_info(env, argv[1 + k], &t[k], &len[k], &p[k], NULL, NULL) != napi_ok || t[k] != want[k]) {
+      napi_throw_type_error(env, NULL,
+                            "aggregatePubkeysFromBits: setSegFirst, segCommittee, setBitsFirst Uint32Array and bits "
+                            "Uint8Array expected");
+      return NULL;
+    }
+  bool no_complement = false;
+  uint32_t out_len = 0;
+  napi_coerce_to_bool(env, argv[5], &argv[5]);
+  napi_get_value_bool(env, argv[5], &no_complement);
+  napi_get_value_uint32(env, argv[6], &out_len);
+  /* shape checks on the host before anything is queued: the arrays are as long as the offsets say (the library checks
+   * the offsets themselves, the committee ids and the bit strings) */
+  const uint32_t *ssf = (const uint32_t*)p[0], *sbf = (const uint32_t*)p[2];
+  int ok = len[0] >= 1 && len[2] == len[0] && len[0] - 1 <= (1u << 20) && (out_len == 48 || out_len == 96);
+  ok = ok && ssf[len[0] - 1] <= len[1] && sbf[len[2] - 1] <= len[3];
+  if (!ok) {
+    napi_throw_range_error(env, "BLSGPU_ERR_ARGS", "aggregatePubkeysFromBits: inconsistent array sizes");
+    return NULL;
+  }
+  BitsCall* a = (BitsCall*)calloc(1, sizeof(BitsCall));
+  a->box = box;
+  a->n_sets = (uint32_t)len[0] - 1;
+  a->flags = no_complement ? BLSGPU_BITS_NO_COMPLEMENT : 0;
+  a->out_len = out_len;
+  a->set_seg_first = (uint32_t*)dup_bytes(p[0], len[0] * 4);
+  a->seg_committee = (uint32_t*)dup_bytes(p[1], len[1] * 4);
+  a->set_bits_first = (uint32_t*)dup_bytes(p[2], len[2] * 4);
+  a->bits = (uint8_t*)dup_bytes(p[3], len[3]);
+  a->out = (uint8_t*)calloc((size_t)a->n_sets * out_len + 1, 1);
+  a->status = (int8_t*)calloc((size_t)a->n_sets + 1, 1);
+  napi_value promise, name;
+  if (!a->set_seg_first || !a->seg_committee || !a->set_bits_first || !a->bits || !a->out || !a->status ||
+      napi_create_promise(env, &a->deferred, &promise) != napi_ok ||
+      napi_create_string_utf8(env, "blsgpu_aggregate_pubkeys_bits", NAPI_AUTO_LENGTH, &name) != napi_ok ||
+      napi_create_async_work(env, NULL, name, bits_execute, bits_complete, a, &a->work) != napi_ok) {
+    bits_free(a);
+    napi_throw_error(env, NULL, "aggregatePubkeysFromBits: could not queue the call");
+    return NULL;
+  }
+  box->agg_pending++;
+  if (napi_queue_async_work(env, a->work) != napi_ok) {
+    box->agg_pending--;
+    napi_delete_async_work(env, a->work);
+    bits_free(a);
+    napi_throw_error(env, NULL, "aggregatePubkeysFromBits: could not queue the call");
+    return NULL;
+  }
+  return promise;
+}
+
 /* debugInject(what, skip, count): blsgpu_debug_inject (test hook; BLSGPU_INJECT_ENTROPY 1, BLSGPU_INJECT_DEVICE 2) */
 static napi_value DebugInject(napi_env env, napi_callback_info info) {
   size_t argc = 3;
@@ -1225,6 +1401,9 @@ static napi_value ModuleInit(napi_env env, napi_value exports) {
       {"verifySameMessage", NULL, VerifySameMessage, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"verifySameMessageAggregate", NULL, VerifySameMessageAggregate, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
       {"aggregateVerify", NULL, AggregateVerify, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
+      {"uploadCommittees", NULL, UploadCommittees, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
+      {"committeesCount", NULL, CommitteesCount, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
+      {"aggregatePubkeysFromBits", NULL, AggregatePubkeysFromBits, NULL, NULL, NULL, (napi_property_attributes)(napi_writable | napi_enumerable | napi_configurable), NULL},
   };
   napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
   /* the fault-injection test hook is exported, by its own definition, only to processes started with

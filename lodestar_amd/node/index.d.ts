@@ -153,6 +153,19 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
   uploadPubkeysCompressed(firstIndex: number, pk48: Uint8Array, opts?: {validate?: boolean}): void;
   /** entries [firstIndex, firstIndex + n) of the device table: 96-byte uncompressed encodings, or 48-byte compressed */
   readPubkeys(firstIndex: number, n: number, opts?: {compressed?: boolean}): Buffer;
+  /** The epoch's shufflings on the device: drops the stored committees with id >= firstCommittee, then stores
+   * `committees` (validator indices into the device table) as ids firstCommittee, firstCommittee + 1, ...; 0 replaces
+   * the store, committeesCount appends.  Synchronous.  An upload that overwrites table rows empties the store. */
+  uploadCommittees(firstCommittee: number, committees: ArrayLike<number>[]): void;
+  readonly committeesCount: number;
+  /** getAggregatedPubkey(set).toBytes() for aggregate sets given as committees plus participation bits (the
+   * uint8Array and bitLen of an ssz BitArray per stored committee), in one device call, off the main thread.  One entry
+   * per set: the key (96 bytes uncompressed, 48 with compressed: true) or the Error "EMPTY_AGGREGATE_ARRAY" for a set
+   * without a participant.  Rejects for malformed input, a call-level failure or once closed. */
+  aggregatePubkeysFromBits(
+    sets: Array<Array<{committee: number; bits: Uint8Array; bitLen: number}>>,
+    opts?: {compressed?: boolean; noComplement?: boolean}
+  ): Promise<Array<Uint8Array | Error>>;
   /** maps a PublicKey object (by identity) to its validator index in the device table */
   registerPubkey(pk: object, index: number): void;
   readonly deviceCount: number;
