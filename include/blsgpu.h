@@ -85,7 +85,7 @@ extern "C" {
  * blsgpu_verify_same_message_agg, blsgpu_same_message_agg_lanes, blsgpu_pubkeys_upload_compressed (with
  * BLSGPU_PK_VALIDATE), blsgpu_pubkeys_read, blsgpu_committees_upload, blsgpu_committees_count,
  * blsgpu_aggregate_pubkeys_bits (with blsgpu_committee_bits_stats and BLSGPU_BITS_NO_COMPLEMENT),
- * blsgpu_committee_bits_mode, blsgpu_committee_bits_lanes. */
+ * blsgpu_committee_bits_mode, blsgpu_committee_bits_lanes, blsgpu_awr_parts. */
 #define BLSGPU_ABI_VERSION 8
 
 /* blsgpu_batch.job_flags bits (reference VerifySignatureOpts, chain/bls/interface.ts:3-18) */
@@ -422,15 +422,31 @@ int blsgpu_randomness_words(uint32_t n, uint64_t seed, uint64_t* words);
  * sum equal to the identity is encoded as the identity.  Groups never affect each other.
  * Malformed arguments (a null pointer other than first_bad, both or neither of pk_bytes / pk_index, an output length,
  * sig_stride < 96, a group_first not as above, a 192-byte signature in a narrower stride) return BLSGPU_ERR_ARGS before
- * anything reaches the device.  Runs on device 0's helper stream, beside verification calls. */
+ * anything reaches the device.  Runs on device 0's helper stream, beside verification calls.
+ * Groups above L t sets are cut into parts, see blsgpu_awr_parts; never changes an answer. */
 int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const uint32_t* group_first,
                                      const uint8_t* pk_bytes, const uint32_t* pk_index, const uint8_t* sigs,
                                      uint32_t sig_stride, const uint32_t* sig_len, uint64_t seed, uint8_t* out_pk,
                                      uint32_t out_pk_len, uint8_t* out_sig, uint32_t out_sig_len, int8_t* status,
                                      uint32_t* first_bad);
 /* Lanes per group the segmented sum of such a call takes (64 = a wave per group with an LDS tree; 32, 16, 8 = lane
- * groups with a shuffle butterfly; 1 = a lane per group): non-increasing in n_groups.  Pure host code. */
+ * groups with a shuffle butterfly; 1 = a lane per group): non-increasing in n_groups.  Pure host code.
+ * Groups above L t sets are cut into parts, see blsgpu_awr_parts; never changes an answer. */
 uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets);
+/* How the randomized sums of a call with these groups (blsgpu_aggregate_with_randomness, blsgpu_verify_same_message,
+ * blsgpu_verify_same_message_agg) are cut.  With L = blsgpu_awr_lanes(n_groups, n) and the chip's 65,536 lanes: a call
+ * with n_groups L > 65,536 is not split; else t is the smallest integer >= 1 with sum over the groups of
+ * max(1, ceil(size_g / (L t))) L <= 65,536, group g is cut into max(1, ceil(size_g / (L t))) consecutive parts of L t
+ * sets (the last one shorter, an empty group is one empty part), each part is summed on L lanes -- no lane takes more
+ * than t sets -- and a second kernel adds each group's parts.  The call is split when some group has more than L t
+ * sets, that is when there are more parts than groups.
+ * *part_sets = L t, or 0 when the call is not split.
+ * *n_parts = parts in all (n_groups when not split).
+ * part_first (nullable, room for max(n_groups, 65536) + 1 entries) receives the parts' first sets and n.
+ * BLSGPU_ERR_ARGS as the calls it describes: a null group_first with n_groups > 0, a null part_sets or n_parts, a
+ * group_first not non-decreasing from 0, more than 1 << 20 sets.  Pure host code. */
+int blsgpu_awr_parts(uint32_t n_groups, const uint32_t* group_first, uint32_t* part_sets, uint32_t* n_parts,
+                     uint32_t* part_first);
 
 #define BLSGPU_SAME_LANE_FORMS 1u /* diagnostics / tests: take the large-call kernel forms whatever the size */
 /* (2u is not a flag: it stays refused) */

@@ -79,7 +79,7 @@ def _tu_deps(src):
     if src.endswith(".cpp"):
         return [os.path.join(CSRC, f) for f in (src, "kernels.h", "batch_rand.hpp", "runtime_internal.hpp",
                                                 "run_plan.hpp", "options.hpp", "call_plan.hpp", "helper_layout.hpp",
-                                                "miller_plan.hpp", "aggverify_plan.hpp", "same_plan.hpp", "committee_plan.hpp",
+                                                "miller_plan.hpp", "aggverify_plan.hpp", "same_plan.hpp", "committee_plan.hpp", "awr_parts.hpp",
                                                 "helper_buffers.hpp")] + [
             os.path.join(ROOT, "include", "blsgpu.h")]
     return [os.path.join(CSRC, src)] + _headers()

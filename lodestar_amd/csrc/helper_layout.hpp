@@ -134,6 +134,22 @@ struct Same {
   }
 };
 
+// What a split call of blsgpu_aggregate_with_randomness or blsgpu_verify_same_message adds (awr_parts.hpp: its G groups
+// cut into n_parts parts), in a buffer of its own (d_parts; hl::Awr and hl::Same are as for a call of the parts' launched
+// lanes), sized with the call's other buffers.  Byte offsets, every field on a 256-byte boundary:
+//   the parts' sum_pk | sum_sig (Jacobian, stride n_parts) | error indices (keys then signatures) | part_first (the
+//   parts' first sets and n, copied up with the inputs) | group_part (the groups' first parts and n_parts, likewise) |
+//   error codes
+struct AwrParts {
+  size_t sum_pk, sum_sig, ek, pf, gp, ec, total, total_words;
+  AwrParts(size_t G, size_t n_parts) {
+    Carve c;
+    sum_pk = c.take(n_parts * kG1J * 4), sum_sig = c.take(n_parts * kG2J * 4), ek = c.take(n_parts * 8);
+    pf = c.take((n_parts + 1) * 4), gp = c.take((G + 1) * 4), ec = c.take(2 * n_parts);
+    total = c.at, total_words = total / 4;
+  }
+};
+
 // blsgpu_verify_same_message, retry phase of nr sets.  d_list (words): list | message indices | iota.  d_ok (bytes):
 // include | code | verdict.  d_fb, d_S, d_F (and d_G): an affine key, a Jacobian signature, an Fp12 value per set.
 struct SameRetry {

@@ -3,6 +3,7 @@
 // table_stream, in Device::helper's buffers; helper_call is the envelope they share and helper_layout.hpp says where
 // every field of their device arenas lies.  The asynchronous verification pipeline is runtime.cpp and pipeline.cpp.
 #include "aggverify_plan.hpp"
+#include "awr_parts.hpp"
 #include "committee_plan.hpp"
 #include "helper_buffers.hpp"
 #include "helper_layout.hpp"
@@ -170,6 +171,52 @@ AwrBuffers same_inputs(Device& d, const Grouped& a, const Layout& l, uint8_t* by
   return ab;
 }
 
+// The randomized sums of both same-message calls when the call is split (awr_parts.hpp; `on` false: it is not, and
+// the sums run as they always did).  Copies the plan's part_first and group_part to their fields of hl::AwrParts `lp`
+// in d_parts -- they go up with the inputs -- and keeps the call's `ab` as the sums over the parts take it: the parts
+// for groups, part-sized sums and errors in d_parts (ab.tab_n is the parts' launched lanes already).
+struct AwrSplit {
+  bool on = false;
+  AwrBuffers parts;
+  const uint32_t* group_part = nullptr;
+  uint32_t L_fold = 1;  // lanes per group of the fold
+};
+AwrSplit awr_split_upload(Slot& sl, const hl::AwrParts& lp, const awr_parts::Plan& ap, const AwrBuffers& ab,
+                          hipStream_t s) {
+  AwrSplit sp;
+  if (!ap.split()) return sp;
+  uint8_t* dp = reinterpret_cast<uint8_t*>(sl.d_parts.p);
+  HIPCHK(hipMemcpyAsync(dp + lp.pf, ap.part_first.data(), ap.part_first.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dp + lp.gp, ap.group_part.data(), ap.group_part.size() * 4, hipMemcpyHostToDevice, s));
+  sp.on = true;
+  sp.L_fold = ap.L_fold;
+  sp.group_part = reinterpret_cast<uint32_t*>(dp + lp.gp);
+  sp.parts = ab;
+  sp.parts.group_first = reinterpret_cast<uint32_t*>(dp + lp.pf);
+  sp.parts.n_groups = ap.n_parts;
+  sp.parts.sum_pk = reinterpret_cast<uint32_t*>(dp + lp.sum_pk);
+  sp.parts.sum_sig = reinterpret_cast<uint32_t*>(dp + lp.sum_sig);
+  sp.parts.err_k = reinterpret_cast<uint32_t*>(dp + lp.ek);
+  sp.parts.err_c = reinterpret_cast<int8_t*>(dp + lp.ec);
+  return sp;
+}
+// sum_pk / sum_sig of `a` and its groups' first errors, on L lanes per group: in one launch, or -- a split call -- over
+// the parts (in a's window scratch) and folded.  Everything after them reads the same fields of `a` either way.
+void awr_sum_pk(const AwrBuffers& a, const AwrSplit& sp, uint32_t L, hipStream_t s) {
+  if (!sp.on) return launch_awr_sum_pk(a, L, s);
+  AwrBuffers p = sp.parts;
+  p.tab = a.tab;
+  launch_awr_sum_pk(p, L, s);
+  launch_awr_fold_pk(p, a, sp.group_part, sp.L_fold, s);
+}
+void awr_sum_sig(const AwrBuffers& a, const AwrSplit& sp, uint32_t L, hipStream_t s) {
+  if (!sp.on) return launch_awr_sum_sig(a, L, s);
+  AwrBuffers p = sp.parts;
+  p.tab = a.tab;
+  launch_awr_sum_sig(p, L, s);
+  launch_awr_fold_sig(p, a, sp.group_part, sp.L_fold, s);
+}
+
 // ---- what blsgpu_verify_same_message and blsgpu_aggregate_verify share ----------------------------------------
 // (their messages are deduplicated and packed by unique_messages, run_plan.hpp.)  The three branches of such a call: signatures on the helper stream s, keys on sb, messages on sc (all s when
 // `serial`: BLSGPU_SAME_SERIAL, diagnostics of the same-message call).  Device::same_st and same_ev are created by
@@ -252,6 +299,7 @@ struct SameCall {
   Branches br;
   PipelineBuffers pb, pm;  // the signature decode, the message branch
   AwrBuffers ab, ab_pk;    // the randomized sums S_g (ab.sum_sig) and P_g (ab.sum_pk; its own window scratch)
+  AwrSplit split;          // how both run when the call is split into parts
   uint32_t *pk_aff, *inv, *F, *Gs;  // per group: the affine P_g, 1 / z of P_g, the Miller value, MillerLoop(-g1, S_g)
   uint8_t *inc, *ok;                // per group: include flag, verdict
   int8_t *code, *gres, *sres;       // per group: code, group_result; per set: set_result
@@ -259,17 +307,18 @@ struct SameCall {
   bool lane(uint32_t n_items) const { return sp::form(n_items, flags) != 0; }
 };
 // Copies the call's inputs to d_in (hl::Same `l`) and says where everything of the group phase lies.
-SameCall same_upload(Device& d, const Branches& br, const Grouped& a, uint32_t flags, const hl::Same& l, uint32_t L,
-                     uint32_t lanes, const uint64_t* words, const std::vector<uint8_t>& umsgs, const uint32_t* gmsg,
-                     const uint32_t* iota) {
+SameCall same_upload(Device& d, const Branches& br, const Grouped& a, uint32_t flags, const hl::Same& l,
+                     const hl::AwrParts& lp, const awr_parts::Plan& ap, uint32_t lanes, const uint64_t* words,
+                     const std::vector<uint8_t>& umsgs, const uint32_t* gmsg, const uint32_t* iota) {
   Slot& sl = d.helper;
   uint8_t* din = sl.d_in.p;
   uint8_t* db = sl.d_bytes.p;
   uint32_t* w = sl.d_work.p;
   const uint32_t G = a.G, U = (uint32_t)(umsgs.size() / 32);
   SameCall c{};
-  c.G = G, c.n = a.n, c.flags = flags, c.L = L, c.br = br;
+  c.G = G, c.n = a.n, c.flags = flags, c.L = ap.L, c.br = br;
   c.ab = same_inputs(d, a, l, db, words, lanes, br.s, c.pb);
+  c.split = awr_split_upload(sl, lp, ap, c.ab, br.s);
   HIPCHK(hipMemcpyAsync(din + l.umsg, umsgs.data(), (size_t)U * 32, hipMemcpyHostToDevice, br.s));
   HIPCHK(hipMemcpyAsync(din + l.gmsg, gmsg, (size_t)G * 4, hipMemcpyHostToDevice, br.s));
   HIPCHK(hipMemcpyAsync(din + l.iota, iota, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, br.s));
@@ -324,10 +373,10 @@ void same_group_items(const SameCall& c) {
       c.br,
       [&](hipStream_t s) {  // signatures: decode + subgroup check (cooperative for small calls), S_g
         launch_sig_decode(c.pb, c.n, s, c.n <= 4096, nullptr, false, true);
-        launch_awr_sum_sig(c.ab, c.L, s);
+        awr_sum_sig(c.ab, c.split, c.L, s);
       },
       [&](hipStream_t sb) {  // keys: P_g and the batch inverses of its z
-        launch_awr_sum_pk(c.ab_pk, c.L, sb);
+        awr_sum_pk(c.ab_pk, c.split, c.L, sb);
         launch_batch_inv(c.ab.sum_pk, c.G, 2 * W_FP, c.inv, c.G, sb);
       },
       [&](hipStream_t sc) {  // messages: H(m) affine, and in the lane form its Miller lines
@@ -451,6 +500,7 @@ int same_message_on_device(Device& d, Slot& sl, hipStream_t s, const Grouped& a,
   const std::vector<uint8_t> umsgs = unique_messages(msgs, G, sp::msg_key(hash_key), gmsg);
   std::vector<uint8_t> h_blk, h_inc;  // (copied to)
   sp::Retry rt;                       // (rt.sets, rt.msg)
+  const awr_parts::Plan ap = awr_parts::plan(a.group_first, G);  // (ap.part_first, ap.group_part)
   for (uint32_t g = 0; g <= G; g++) iota[g] = g;
   const uint32_t U = (uint32_t)(umsgs.size() / 32);
   h.st.unique_messages = U;
@@ -458,14 +508,16 @@ int same_message_on_device(Device& d, Slot& sl, hipStream_t s, const Grouped& a,
     const Branches br = branches(d, s, same_serial());
     const auto t0 = std::chrono::steady_clock::now();
     const bool lane_g = sp::form(G, flags) != 0;
-    const uint32_t L = awr_lanes(G, n), lanes = awr_launch_lanes(G, L);
+    const uint32_t lanes = awr_launch_lanes(ap.n_parts, ap.L);  // (n_parts = G unless the call is split)
     const hl::Same l(G, n, U, a.sig_stride, a.pk_bytes != nullptr, lanes);
+    const hl::AwrParts lp(G, ap.n_parts);
     // every buffer of the group phase grows here, while none of the three streams has work (each call ends with all
     // of them synchronized); the retry phase grows only buffers the group phase does not use, after its synchronize
     sl.d_in.ensure(l.in_total);
     sl.d_bytes.ensure(l.bytes_total);
     sl.d_work.ensure(l.work_words);
     if (lane_g) sl.d_lines.ensure(l.lines_words);
+    if (ap.split()) sl.d_parts.ensure(lp.total_words);
     // BLSGPU_SAME_BLOCK_CHECK: the block phase's buffers grow here too; the descent's, like the retry phase's, after
     // the synchronize before it, and they are buffers no other phase uses
     const uint32_t NB = sp::blocks(G, flags);
@@ -478,7 +530,7 @@ int same_message_on_device(Device& d, Slot& sl, hipStream_t s, const Grouped& a,
     const hl::SameAgg la(G, n, agg ? agg->out_sig_len : 0);
     if (agg) sl.d_msmB.ensure(la.total_words);
     sized = true;
-    SameCall c = same_upload(d, br, a, flags, l, L, lanes, words.data(), umsgs, gmsg.data(), iota.data());
+    SameCall c = same_upload(d, br, a, flags, l, lp, ap, lanes, words.data(), umsgs, gmsg.data(), iota.data());
     uint8_t* da = agg ? reinterpret_cast<uint8_t*>(sl.d_msmB.p) : nullptr;
     if (agg && agg->include && n) HIPCHK(hipMemcpyAsync(da + la.inc, agg->include, n, hipMemcpyHostToDevice, s));
     same_group_items(c);
@@ -733,22 +785,27 @@ int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const u
   Grouped a{n_groups, group_first, sigs, sig_stride, sig_len, pk_bytes, pk_index};
   if (int e = check_group_layout(a)) return e;
   const uint32_t n = a.n, G = n_groups;
+  const awr_parts::Plan ap = awr_parts::plan(group_first, G);  // copied from: it lives until the final synchronize
   return helper_call(ctx, true, [&](Device& d, Slot& sl, hipStream_t s) -> int {
     std::vector<uint64_t> words;
     uint64_t hash_key = 0;
     if (int e = same_begin(d, a, seed, words, hash_key)) return e;
-    const uint32_t L = awr_lanes(G, n), lanes = awr_launch_lanes(G, L);
+    const uint32_t L = ap.L, lanes = awr_launch_lanes(ap.n_parts, L);  // (n_parts = G unless the call is split)
     const hl::Awr l(G, n, sig_stride, pk_bytes != nullptr, out_pk_len, out_sig_len, lanes);
+    const hl::AwrParts lp(G, ap.n_parts);
     sl.d_in.ensure(l.total);
     sl.d_work.ensure(l.work_words);
+    if (ap.split()) sl.d_parts.ensure(lp.total_words);
     uint8_t* din = sl.d_in.p;
     PipelineBuffers pb;
     const AwrBuffers ab = same_inputs(d, a, l, din, words.data(), lanes, s, pb);
+    const AwrSplit split = awr_split_upload(sl, lp, ap, ab, s);
     int8_t* d_gst = reinterpret_cast<int8_t*>(din + l.gst);
     uint32_t* d_fb = reinterpret_cast<uint32_t*>(din + l.fb);
     // small calls take the cooperative subgroup check, as small verification runs do
     launch_sig_decode(pb, n, s, n <= 4096, nullptr, false, true);
-    launch_awr_sums(ab, L, s);
+    awr_sum_pk(ab, split, L, s);
+    awr_sum_sig(ab, split, L, s);
     launch_awr_serialize(ab, din + l.opk, out_pk_len, din + l.osig, out_sig_len, d_gst, d_fb, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_pk, din + l.opk, (size_t)G * out_pk_len, hipMemcpyDeviceToHost, s));
@@ -761,6 +818,23 @@ int blsgpu_aggregate_with_randomness(blsgpu_ctx* ctx, uint32_t n_groups, const u
 }
 
 uint32_t blsgpu_awr_lanes(uint32_t n_groups, uint32_t n_sets) { return awr_lanes(n_groups, n_sets); }
+
+int blsgpu_awr_parts(uint32_t n_groups, const uint32_t* group_first, uint32_t* part_sets, uint32_t* n_parts,
+                     uint32_t* part_first) {
+  if ((n_groups && !group_first) || !part_sets || !n_parts) return BLSGPU_ERR_ARGS;
+  uint32_t n = 0;
+  if (n_groups)  // (a call of no groups is accepted before its group_first is read, as the calls described accept it)
+    if (int e = check_offsets(group_first, n_groups, n)) return e;
+  const awr_parts::Plan ap = awr_parts::plan(group_first, n_groups);
+  *part_sets = ap.part_sets;
+  *n_parts = ap.n_parts;
+  if (part_first) {
+    const uint32_t* src = ap.split() ? ap.part_first.data() : group_first;
+    if (n_groups) memcpy(part_first, src, ((size_t)ap.n_parts + 1) * 4);
+    else part_first[0] = 0;
+  }
+  return BLSGPU_OK;
+}
 
 // ---- one-call same-message verification: the rules are same_plan.hpp, the phases and their driver are above
 uint32_t blsgpu_same_message_form(uint32_t n_items, uint32_t flags) { return sp::form(n_items, flags); }

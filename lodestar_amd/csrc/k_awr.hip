@@ -2,7 +2,9 @@
 // G1 and S = sum r_k sig_k in G2 over the sets' trusted keys (table entries or 96-byte encodings) and the signatures
 // k_sig_decode left in sig_aff (k_sig.hip), r_k the batch scalar of set k's word (k_common.hpp jac_mul_scalar_word),
 // and the serialization of both sums.  One kernel template serves both groups (F = fp: keys, fp2: signatures); the
-// lanes of a group combine by the forms of seg_sum.hpp, as k_sigagg.hip does.
+// lanes of a group combine by the forms of seg_sum.hpp, as k_sigagg.hip does.  A call with groups larger than their
+// lanes take at one go is split (awr_parts.hpp): the same kernel sums parts of the groups and k_awr_fold adds each
+// group's parts, so that a large group runs on as many waves as the chip has free.
 #include "k_common.hpp"
 #include "seg_sum.hpp"
 
@@ -108,6 +110,57 @@ STAGE_KERNEL_W(1) void k_awr_sum(AwrBuffers a) {
   if (on && t == 0) awr_store<F>(a, g, acc, my_err_k, my_err);
 }
 
+// ---- split calls (awr_parts.hpp): k_awr_sum ran over the parts; group g's sum is the sum of its parts -------------
+// One lane's share of the parts [first, last) of a group: parts first + t, first + t + L, ...  Each goes through the
+// complete addition: two parts' sums may be equal, opposite or the identity.  The error is the lowest set index.
+template <class F>
+BLS_INL void awr_fold_strided(const AwrBuffers& p, uint32_t first, uint32_t last, uint32_t t, uint32_t L, jac<F>& acc,
+                              uint32_t& err_k, int& err) {
+  constexpr int which = sizeof(F) == sizeof(fp) ? 0 : 1;
+  const uint32_t* sums = awr_sums(p, (const jac<F>*)0);
+#pragma unroll 1
+  for (uint32_t q = first + t; q < last; q += L) {
+    jac<F> P;
+    uint32_t* d = reinterpret_cast<uint32_t*>(&P);
+#pragma unroll
+    for (int w = 0; w < (int)(sizeof(jac<F>) / 4); w++) d[w] = sums[(size_t)w * p.n_groups + q];
+    acc = jac_add(acc, P);
+    const uint32_t k = p.err_k[which * p.n_groups + q];
+    if (k < err_k) {
+      err_k = k;
+      err = p.err_c[which * p.n_groups + q];
+    }
+  }
+}
+
+// L lanes per group, the forms of k_sigagg.hip: 64 = a wave per group with the LDS tree, 32 / 16 / 8 = lane groups with
+// the shuffle butterfly, 1 = a lane per group.  A few additions per lane: no occupancy bound is asked for.
+template <class F, int L>
+__global__ __launch_bounds__(WAVE) void k_awr_fold(AwrBuffers p, AwrBuffers a, const uint32_t* group_part) {
+  const uint32_t q = blockIdx.x * WAVE + threadIdx.x;
+  const uint32_t t = q % L, g = q / L;
+  const bool on = g < a.n_groups;  // whole groups: L divides WAVE, so a group never straddles a wave
+  const uint32_t first = on ? group_part[g] : 0, last = on ? group_part[g + 1] : 0;
+  jac<F> acc = jac_infinity<F>();
+  uint32_t my_err_k = 0xffffffffu;
+  int my_err = 0;
+  awr_fold_strided<F>(p, first, last, t, L, acc, my_err_k, my_err);
+  if constexpr (L == WAVE) {
+    __shared__ uint32_t red[SEG_SLOTS * (sizeof(jac<F>) / 4)];
+    __shared__ uint32_t err_k[WAVE];
+    __shared__ int32_t err_c[WAVE];
+    uint32_t bk;
+    int bc;
+    seg_wave_first_error(err_k, err_c, t, my_err_k, my_err, bk, bc);
+    if (last - first > 1) seg_wave_tree(acc, red, t);  // (uniform per workgroup)
+    my_err_k = bk;
+    my_err = bc;
+  } else {
+    seg_butterfly<F, L>(acc, my_err_k, my_err);
+  }
+  if (on && t == 0) awr_store<F>(a, g, acc, my_err_k, my_err);
+}
+
 // Both sums' toBytes(), one lane per group (one Fp and one Fp2 inversion each): P in 48 (compressed) or 96 bytes, S in
 // 96 (compressed) or 192; the identity encoding for a sum equal to the identity, zeros for a rejected or empty group.
 // The group's status is EMPTY_AGGREGATE, or the code of its lowest-index rejected set -- the key's when both the key
@@ -176,6 +229,29 @@ void launch_awr_sum_sig(const AwrBuffers& a, uint32_t L, hipStream_t s) { launch
 void launch_awr_sums(const AwrBuffers& a, uint32_t L, hipStream_t s) {
   launch_awr_sum_pk(a, L, s);
   launch_awr_sum_sig(a, L, s);
+}
+template <class F>
+static void launch_awr_fold(const AwrBuffers& p, const AwrBuffers& a, const uint32_t* group_part, uint32_t L,
+                            hipStream_t s) {
+  if (!a.n_groups) return;
+  const dim3 grid(awr_launch_lanes(a.n_groups, L) / WAVE);
+#define AWR_FOLD(l) hipLaunchKernelGGL((k_awr_fold<F, l>), grid, dim3(WAVE), 0, s, p, a, group_part)
+  switch (L) {
+    case 64: AWR_FOLD(64); break;
+    case 32: AWR_FOLD(32); break;
+    case 16: AWR_FOLD(16); break;
+    case 8: AWR_FOLD(8); break;
+    default: AWR_FOLD(1); break;
+  }
+#undef AWR_FOLD
+}
+void launch_awr_fold_pk(const AwrBuffers& parts, const AwrBuffers& a, const uint32_t* group_part, uint32_t L,
+                        hipStream_t s) {
+  launch_awr_fold<fp>(parts, a, group_part, L, s);
+}
+void launch_awr_fold_sig(const AwrBuffers& parts, const AwrBuffers& a, const uint32_t* group_part, uint32_t L,
+                         hipStream_t s) {
+  launch_awr_fold<fp2>(parts, a, group_part, L, s);
 }
 void launch_awr_serialize(const AwrBuffers& a, uint8_t* out_pk, uint32_t out_pk_len, uint8_t* out_sig,
                           uint32_t out_sig_len, int8_t* status, uint32_t* first_bad, hipStream_t s) {

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <vector>
 
+#include "awr_parts.hpp"
+
 // Word counts of the SoA records (element i, word w at base[w * stride + i])
 #define W_FP 14
 #define W_G1A (2 * W_FP)
@@ -291,20 +293,7 @@ struct AwrBuffers {
   int8_t* err_c;      // [2 n_groups]: its code
 };
 #define AWR_TAB_WORDS (9 * W_G2J)
-// Lanes per group of the segmented randomized sum (blsgpu_awr_lanes).  A set costs two scalar multiplications (~50
-// point operations each), a combine level one Jacobian addition per sum, so -- unlike sig_agg_lanes -- a lane per set
-// pays off from two sets on: the fewest lanes of 8, 16, 32, 64 that cover the mean group size (one lane for one-set
-// groups), capped by the group count: the kernels run one wave per SIMD (the scaling takes the whole register file),
-// so the chip holds 1,024 waves = 65,536 lanes at a time and lanes beyond that only queue: the most lanes of 64, 32,
-// 16, 8 with n_groups * L <= 65,536, then one lane per group.  Non-increasing in n_groups for a given n_sets.
-inline uint32_t awr_lanes(uint32_t n_groups, uint32_t n_sets) {
-  if (n_groups == 0) return 1;
-  const uint64_t n = n_groups, lanes = 1024 * 64;
-  const uint32_t by_count = n * 64 <= lanes ? 64 : n * 32 <= lanes ? 32 : n * 16 <= lanes ? 16 : n * 8 <= lanes ? 8 : 1;
-  const uint64_t mean = ((uint64_t)n_sets + n - 1) / n;
-  const uint32_t by_size = mean <= 1 ? 1 : mean <= 8 ? 8 : mean <= 16 ? 16 : mean <= 32 ? 32 : 64;
-  return by_count < by_size ? by_count : by_size;
-}
+// (the lanes per group, awr_lanes, and the cut of large groups into parts are awr_parts.hpp)
 uint32_t awr_launch_lanes(uint32_t n_groups, uint32_t L);
 // sum_pk / sum_sig and the per-group first errors, on L lanes per group (a.tab_n = awr_launch_lanes(n_groups, L))
 void launch_awr_sums(const AwrBuffers& a, uint32_t L, hipStream_t s);
@@ -312,6 +301,15 @@ void launch_awr_sums(const AwrBuffers& a, uint32_t L, hipStream_t s);
 // but a.tab, so two copies of `a` with different window scratch may run on two streams at once.
 void launch_awr_sum_pk(const AwrBuffers& a, uint32_t L, hipStream_t s);
 void launch_awr_sum_sig(const AwrBuffers& a, uint32_t L, hipStream_t s);
+// A split call (awr_parts.hpp): the sums above run over the parts -- `parts` is the call's `a` with group_first = the
+// parts' first sets, n_groups = the parts and sum_pk / sum_sig / err_k / err_c part-sized -- and these fold them: group
+// g's parts are [group_part[g], group_part[g + 1]); its Jacobian sum and its first error (the lowest set index over
+// the parts) go where the unsplit sums leave them, a.sum_pk / a.sum_sig / a.err_k / a.err_c (stride a.n_groups).  The
+// fold is a plain segmented sum of the parts on L = awr_parts::fold_lanes(..) lanes per group (64, 32, 16, 8 or 1).
+void launch_awr_fold_pk(const AwrBuffers& parts, const AwrBuffers& a, const uint32_t* group_part, uint32_t L,
+                        hipStream_t s);
+void launch_awr_fold_sig(const AwrBuffers& parts, const AwrBuffers& a, const uint32_t* group_part, uint32_t L,
+                         hipStream_t s);
 // One-call same-message verification (k_same.hip, blsgpu_verify_same_message).
 // per group: pk_aff (W_G1A, stride n_groups) = sum_pk times inv = 1 / z (launch_batch_inv), code = the group's AWR
 // status, include = accepted by AWR with a finite P

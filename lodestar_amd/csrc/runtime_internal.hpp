@@ -195,6 +195,7 @@ struct Slot {
   DevBuf<uint32_t> d_work, d_lines, d_S, d_F, d_G, d_list, d_msmB, d_msmW, d_fb;
   DevBuf<uint32_t> d_fkeep;  // the batch pass's per-set Miller values, kept for the fallback (run_plan.hpp Forms::keep_f)
   DevBuf<uint32_t> d_fseg;   // step segments: the (segment, group) heads of the F tree before their fold (k_f_fold)
+  DevBuf<uint32_t> d_parts;  // helper slot: what a split same-message call adds (helper_layout.hpp AwrParts)
   HostBuf<uint8_t> h_in, h_res, h_ok;
   HostBuf<uint32_t> h_list;
   // The slot's own stream for the fallback of its runs (lowest priority).  A failed group's checks used to run on the
@@ -210,12 +211,12 @@ struct Slot {
   // whenever it grows a buffer (its dispatcher waits for each run), so only this ordering matters
   void set_stream(hipStream_t st) {
     for (auto* b : {&d_in, &d_res, &d_bytes, &d_ok, &d_fbflags}) b->st = st;
-    for (auto* b : {&d_work, &d_lines, &d_S, &d_F, &d_G, &d_list, &d_msmB, &d_msmW, &d_fb, &d_fkeep, &d_fseg}) b->st = st;
+    for (auto* b : {&d_work, &d_lines, &d_S, &d_F, &d_G, &d_list, &d_msmB, &d_msmW, &d_fb, &d_fkeep, &d_fseg, &d_parts}) b->st = st;
   }
   void release_all() {
     d_in.release(); d_res.release(); d_bytes.release(); d_ok.release(); d_fbflags.release();
     d_work.release(); d_lines.release(); d_S.release(); d_F.release(); d_list.release();
-    d_msmB.release(); d_msmW.release(); d_fb.release(); d_G.release(); d_fkeep.release(); d_fseg.release();
+    d_msmB.release(); d_msmW.release(); d_fb.release(); d_G.release(); d_fkeep.release(); d_fseg.release(); d_parts.release();
     h_in.release(); h_res.release(); h_ok.release(); h_list.release();
   }
 };

@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = [
     "blsgpu_aggregate_pubkeys_bits",
     "blsgpu_committee_bits_mode",
     "blsgpu_committee_bits_lanes",
+    "blsgpu_awr_parts",
 ]
 PK_VALIDATE = 1  # BLSGPU_PK_VALIDATE: the uploaded keys are untrusted, KeyValidate each
 BITS_NO_COMPLEMENT = 1  # BLSGPU_BITS_NO_COMPLEMENT: diagnostics / tests, always sum the participants
@@ -229,6 +230,8 @@ def load():
     lib.blsgpu_aggregate_with_randomness.restype = ctypes.c_int
     lib.blsgpu_awr_lanes.argtypes = [u32, u32]
     lib.blsgpu_awr_lanes.restype = u32
+    lib.blsgpu_awr_parts.argtypes = [u32, vp, vp, vp, vp]
+    lib.blsgpu_awr_parts.restype = ctypes.c_int
     lib.blsgpu_verify_same_message.argtypes = [vp, u32, vp, vp, vp, vp, vp, u32, vp, ctypes.c_uint64, u32, vp, vp, vp]
     lib.blsgpu_verify_same_message.restype = ctypes.c_int
     lib.blsgpu_same_message_form.argtypes = [u32, u32]
@@ -331,6 +334,27 @@ def awr_lanes(n_groups, n_sets):
     """Lanes per group blsgpu_aggregate_with_randomness gives a call of this shape (C-ABI blsgpu_awr_lanes, pure host
     code): 64, 32, 16, 8 or 1."""
     return int(load().blsgpu_awr_lanes(n_groups, n_sets))
+
+
+def awr_parts(group_first):
+    """How the randomized sums of a same-message call with these groups are cut (C-ABI blsgpu_awr_parts, pure host
+    code): (part_sets, part_first).  part_sets = L t sets per part, or 0 when the call is not split; part_first = the
+    parts' first sets and n, a uint32 array of n_parts + 1 entries (group_first itself when not split).  ValueError
+    for a group_first the calls would refuse."""
+    gf = np.ascontiguousarray(group_first, dtype=np.int64)
+    if gf.ndim != 1 or len(gf) == 0:
+        raise ValueError("group_first needs n_groups + 1 >= 1 entries")
+    if (gf < 0).any() or (gf > 0xFFFFFFFF).any():
+        raise ValueError("group_first entries must be set counts")
+    gf = gf.astype(np.uint32)
+    n_groups = len(gf) - 1
+    out = np.zeros(max(n_groups, 65536) + 1, np.uint32)
+    part_sets, n_parts = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    rc = load().blsgpu_awr_parts(n_groups, gf.ctypes.data, ctypes.addressof(part_sets), ctypes.addressof(n_parts),
+                                 out.ctypes.data)
+    if rc != OK:
+        raise ValueError(f"blsgpu_awr_parts -> {code_name(rc)}")
+    return int(part_sets.value), out[: n_parts.value + 1].copy()
 
 
 def same_message_form(n_items, flags=0):
